@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: under torch.distributed.run, or plain - it then starts its
                                                           own N ranks through torch.distributed.run on 127.0.0.1)
+                    [--full] [--dump-outputs DIR]
 
 One "step" renders one synthetic 800x800 Blender-chair frame (BASELINE.json configs[2]: 640,000 rays,
 64 coarse + 128 importance samples, separate coarse/fine networks, white background, eval mode)
@@ -15,13 +16,16 @@ acc spans (0, 1] on this frame (oracle/calibration.py) - with the plain seeds ev
 frame is all background, so neither sample_pdf nor compositing would see a non-trivial input.  After the timed
 region a strided sample of the TIMED frame is compared with the CPU oracle (== reference): rank statistics against
 the oracle's own fp32-vs-fp64 distance on every sampled ray plus the plain 1e-4 tolerance on the reproducible ones;
-the run fails if that does not hold ("parity" in the JSON line).
+the run fails if that does not hold ("parity" in the JSON line).  That check and every other leg below runs with --full only: a
+plain run sets up, warms up, times the K steps and prints the headline fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  --dump-outputs DIR writes the maps the last timed step rendered as DIR/<map>.npy (float32, the whole frame;
+the inputs are the same bits on every run).
 
 The MLP GEMMs run in the package's default arithmetic (INERF_PRECISION, default "f16x3": fp32 operands
 split into f16 hi/lo pairs, 3 f16 MFMA products per MAC, fp32 accumulation - same error against fp64
 as the exact-fp32 MFMA kernel); "dtype" says which one ran.
 
-Prints ONE JSON line (rank 0) with the bench contract's fields plus
+Prints ONE JSON line (rank 0) with the bench contract's fields, with --full plus
   "roofline"     : algorithmic TFLOP/s (2 x 659,456 MAC per sample point) of the dominant kernel from
                    HIP-event timings of its launches at this workload's sizes.  For the f16x3 kernel the
                    peak is the dense f16 MFMA peak divided by the 3 products it issues per fp32 MAC
@@ -231,6 +235,18 @@ def parity_report(frame, sel, o32, o64, rays_s, sd_f):
     return rep, problems
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """The maps one timed step returns (the whole frame, 12 floats per ray = 30.7 MB) as ``out_dir/<map>.npy`` in float32."""
+    maps = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in frame.items()}
+    assert sum(a.nbytes for a in maps.values()) <= DUMP_CAP_BYTES, {k: a.shape for k, a in maps.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in maps.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def events_ms(fn, reps=1):
     """Average GPU time of ``fn()`` in ms by HIP events on the current stream (torch's current stream IS the stream the
     launchers enqueue on)."""
@@ -275,7 +291,15 @@ def main():
                     help="time the CPU oracle on the 4077-ray parity sample only (default: SURVEY.md 8d - one 32768-ray chunk x 3, ~3 min)")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="(the default since round 3; accepted for old command lines)")
     ap.add_argument("--no-extras", action="store_true", help="skip configs / train_step / exact-fp32 extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks: reference chunking, frame costs, rooflines, "
+                         "the exact-fp32 path, the range fallback, configs, train_step, cpu_baseline and the parity check against the oracle "
+                         "(without it: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps the last timed step rendered as DIR/<map>.npy (float32, the whole frame)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU) and hand back rank 0's line + exit code
@@ -405,6 +429,29 @@ def main():
         assert torch.equal(lo, hi), "ranks disagree on the gathered frame"
     rays_per_s = n_total * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
+    prec = _capi.default_precision()
+    f16 = prec == _capi.PREC_F16X3
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame)
+    head = {"metric": "rays/sec (64+128 samples/ray)", "value": rays_per_s, "unit": "rays/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32 (operands split into f16 hi+lo, 3 f16 MFMA products per MAC, fp32 accumulate)" if f16 else "f32",
+            "data": "synthetic",
+            "config": {"workload": "Blender chair 800x800 frame (640000 rays), 64 coarse + 128 importance samples, "
+                                   "coarse+fine intrinsic NeRF (D=8, W=256), white_bkgd, eval mode, default-init weights "
+                                   "(seeds 0/1) with the density head calibrated so that acc spans (0, 1]",
+                       "rays_per_step": n_total, "parallelism": f"ray-sharded x{world}",
+                       "gather": "all_gather of 12 floats/ray" if world > 1 else "none"},
+            "full": args.full}
+    if not args.full:
+        # the headline alone: everything below (extra legs, rooflines, CPU baseline, parity against the oracle) is --full
+        if rank == 0:
+            json_out.write(json.dumps(head) + "\n")
+            json_out.flush()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the same frame through the reference's own call shape: chunk = 32768 (run_nerf.py:167, :559) ----
     # object_level.batchify_rays merges eval-mode chunks up to a workspace cap (results are bit-identical for any chunking), so a
@@ -542,8 +589,6 @@ def main():
         coarse_ms = sum(durs[0::2]) / len(durs[0::2])          # the coarse-shaped launches alone = configs[1]'s kernel
         return out, (z_c, coarse_ms)
 
-    prec = _capi.default_precision()
-    f16 = prec == _capi.PREC_F16X3
     roofline, (z_coarse, coarse_launch_ms) = kernel_roofline(prec, max(1, args.steps))
     roofline_f32 = roofline if prec == _capi.PREC_F32 else (kernel_roofline(_capi.PREC_F32, max(1, args.steps))[0] if not args.no_extras else None)
 
@@ -1063,17 +1108,8 @@ def main():
 
     if rank == 0:
         json_out.write(json.dumps({
-            "metric": "rays/sec (64+128 samples/ray)", "value": rays_per_s, "unit": "rays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None,
+            **head,
             "value_reference_chunking": None if ref_chunking is None else ref_chunking["value"], "reference_chunking": ref_chunking,
-            "dtype": "f32 (operands split into f16 hi+lo, 3 f16 MFMA products per MAC, fp32 accumulate)" if f16 else "f32",
-            "data": "synthetic",
-            "config": {"workload": "Blender chair 800x800 frame (640000 rays), 64 coarse + 128 importance samples, "
-                                   "coarse+fine intrinsic NeRF (D=8, W=256), white_bkgd, eval mode, default-init weights "
-                                   "(seeds 0/1) with the density head calibrated so that acc spans (0, 1]",
-                       "rays_per_step": n_total, "parallelism": f"ray-sharded x{world}",
-                       "gather": "all_gather of 12 floats/ray" if world > 1 else "none"},
             "roofline": roofline, "strict_fp32": strict, "roofline_f32_kernel": roofline_f32, "exact_f32_path": exact, "parity": parity,
             "configs": configs, "frame_costs": frame_costs, "f16_range_fallback": fallback, "train_step": train, "cpu_baseline": cpu}) + "\n")
         json_out.flush()

@@ -12,9 +12,9 @@ python -c 'import __graft_entry__ as g; g.build()' || exit 1
 # 0. the GPU suite on this code
 timeout 1200 python -m pytest tests -m gpu -q -x > $OUT/${tag}_pytest_gpu.log 2>&1; tail -3 $OUT/${tag}_pytest_gpu.log
 # 1. the benchmark as the driver runs it (with the CPU oracle: parity + cpu_baseline)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err
+timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err || exit 1
 # 2. the same under rocprofv3 --kernel-trace --stats (no CPU legs: the profiler only sees the GPU)
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/${tag}_bench -o bench -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${tag}_bench_under_rocprof.json 2> $OUT/${tag}_bench_under_rocprof.err )
+( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/${tag}_bench -o bench -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/${tag}_bench_under_rocprof.json 2> $OUT/${tag}_bench_under_rocprof.err ) || exit 1
 find $OUT/prof/${tag}_bench -name "*kernel_stats.csv" -exec cp {} $OUT/${tag}_bench_kernel_stats.csv \;
 # 3. PMC passes on the dominant kernel at the benchmark's launch shape (640 000 rays x 192 samples), one counter group per pass
 export BENCH_SIZE="--rays 640000 --iters 2" BENCH_ARGS="--precision f16x3"
@@ -47,7 +47,7 @@ timeout 300 bash scripts/pmc_pass.sh ${tag}_lay GRBM_GUI_ACTIVE SQ_WAVE_CYCLES S
 python scripts/pmc_report.py $OUT/prof/${tag}_lay k_linear > $OUT/${tag}_layered_pmc.txt 2>&1
 # 7. two ranks sharing this GPU over gloo (sharding + gather logic of bench.py --gpus N, both configs; numbers mean nothing): plain
 #    `python bench.py --gpus 2` - it starts its own ranks through torch.distributed.run on 127.0.0.1
-INERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --cpu-baseline-quick > $OUT/${tag}_bench_n2_shared.json 2> $OUT/${tag}_bench_n2_shared.err
+INERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --cpu-baseline-quick --full > $OUT/${tag}_bench_n2_shared.json 2> $OUT/${tag}_bench_n2_shared.err
 # 8. trained-network evidence
 timeout 900 python scripts/fit_synthetic.py --out $OUT/${tag}_trained_network.txt > $OUT/${tag}_fit.log 2>&1
 # 9. full-frame PSNR delta (needs gpurun_in/psnr_full_frame_oracle.npz from `scripts/psnr_full_frame.py --oracle` in the build container)

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out
 cd $REPO
 python -c 'import __graft_entry__ as g; g.build(); g.smoke()' > $OUT/${tag}_final_smoke.txt 2>&1; tail -1 $OUT/${tag}_final_smoke.txt
 ( time timeout 1500 python -m pytest tests -m gpu -q -x ) > $OUT/${tag}_final_pytest_gpu.log 2>&1; tail -5 $OUT/${tag}_final_pytest_gpu.log
-python bench.py --steps 5 --warmup 1 > $OUT/${tag}_final_bench.json 2> $OUT/${tag}_final_bench.err; tail -c 300 $OUT/${tag}_final_bench.err
+python bench.py --steps 5 --warmup 1 --full > $OUT/${tag}_final_bench.json 2> $OUT/${tag}_final_bench.err; tail -c 300 $OUT/${tag}_final_bench.err
 [ -n "$FINAL_SHORT" ] && exit 0          # (smoke + suite + bench only)
 export BENCH_SIZE="--rays 640000 --iters 2" BENCH_ARGS="--precision f16x3"
 bash scripts/pmc_pass.sh ${tag}f_fetch FETCH_SIZE

@@ -6,8 +6,8 @@ export TMPDIR=/tmp; REPO=${GRAFT_REPO_ROOT:-$PWD}; OUT=$REPO/gpurun_out; L=$REPO
 lease_a() {
 python -c 'import __graft_entry__ as g; g.build()' || exit 1
 timeout 600 python -m pytest tests/test_graphs_gpu.py tests/test_dropin_gpu.py -m gpu -q -x > $OUT/r05a_pytest.log 2>&1; tail -5 $OUT/r05a_pytest.log
-( time timeout 900 python bench.py --steps 5 --warmup 1 ) > $OUT/r05a_bench.json 2> $OUT/r05a_bench.err; tail -c 600 $OUT/r05a_bench.err
-( time INERF_BENCH_SHARE_GPU=1 timeout 600 python bench.py --gpus 2 --steps 1 --warmup 1 --cpu-baseline-quick ) > $OUT/r05a_bench_n2_self.json 2> $OUT/r05a_bench_n2_self.err; echo "n2 rc=$?"; tail -c 400 $OUT/r05a_bench_n2_self.err
+( time timeout 900 python bench.py --steps 5 --warmup 1 --full ) > $OUT/r05a_bench.json 2> $OUT/r05a_bench.err; tail -c 600 $OUT/r05a_bench.err
+( time INERF_BENCH_SHARE_GPU=1 timeout 600 python bench.py --gpus 2 --steps 1 --warmup 1 --cpu-baseline-quick --full ) > $OUT/r05a_bench_n2_self.json 2> $OUT/r05a_bench_n2_self.err; echo "n2 rc=$?"; tail -c 400 $OUT/r05a_bench_n2_self.err
 python scripts/bench_train_kernels.py > $OUT/r05a_train_kernels.txt 2>&1; tail -8 $OUT/r05a_train_kernels.txt
 python - <<'PY'
 import json

@@ -15,5 +15,5 @@ done > $OUT/r06_ssr_t128_ab.txt 2>&1
 cat $OUT/r06_ssr_t128_ab.txt
 for c in 5 28 32; do echo "[C=$c default] $(python scripts/bench_ssr_frame.py --frames 4 --classes $c 2>&1 | grep -v amdgpu | tail -1 | cut -c1-170)"; done >> $OUT/r06_ssr_t128_ab.txt 2>&1
 tail -3 $OUT/r06_ssr_t128_ab.txt
-INERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --cpu-baseline-quick > $OUT/r06_bench_n2_shared.json 2> $OUT/r06_bench_n2_shared.err; tail -c 600 $OUT/r06_bench_n2_shared.err; python -c "
+INERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --cpu-baseline-quick --full > $OUT/r06_bench_n2_shared.json 2> $OUT/r06_bench_n2_shared.err; tail -c 600 $OUT/r06_bench_n2_shared.err; python -c "
 import json; d=json.loads(open('$OUT/r06_bench_n2_shared.json').read().strip().split(chr(10))[-1]); print('n2 shared: value', d['value'], 'n_gpus', d['n_gpus'], 'ref chunking', d['reference_chunking']['bit_identical_to_the_timed_frame'], 'ssr', d['configs']['ssr_room0_320x240'].get('checksum_identical_on_all_ranks'))"
