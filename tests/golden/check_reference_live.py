@@ -3,8 +3,9 @@
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/check_reference_live.py [--cases 12] [--seed 0]
 
-The committed fixtures pin the oracle on eleven hand-picked configurations; this script sweeps what they do not: random
-ray counts (1 .. 40), sample counts, importance counts (0 included), white background / lindisp / perturb / noise flags,
+The committed fixtures pin the oracle on hand-picked configurations; this script sweeps what they do not: random
+ray counts (1 .. 40), sample counts, importance counts (0 and 64 included), white background / lindisp / perturb / noise flags,
+the chair camera or NDC rays of an LLFF camera, uniform or Gaussian (negative) raw noise fed through the pytest hooks,
 class counts, the endpoint feature, default `nn.Linear` initialisation instead of the closed-form weights, unconditioned
 rays - and asserts oracle == reference (<= 2e-6, NaN patterns included) on every returned tensor, for
 `object_level/run_nerf.render_rays`, `SSRTrainer.render_rays` and `Cluster_Manager.dest_color / dest_class`.
@@ -30,11 +31,15 @@ import oracle  # noqa: E402
 
 def object_case(run_nerf, H_ref, rng, idx):
     n = int(rng.integers(1, 41))
-    n_imp = int(rng.choice([0, 1, 16, 128]))
+    n_imp = int(rng.choice([0, 1, 16, 64, 128]))
     s = int(rng.choice([4, 7, 64] if n_imp > 0 else [2, 7, 64]))      # the reference itself needs >= 3 coarse samples to resample
     white, lindisp, train = bool(rng.integers(2)), bool(rng.integers(2)), bool(rng.integers(2))
+    # the LLFF configs' camera: NDC rays, near 0, far 1 (with lindisp the reference divides by near = 0: not a config it runs);
+    # their raw noise is torch.randn's, negative about half the time
+    ndc, gauss = bool(rng.integers(2)), bool(rng.integers(2))
+    lindisp = lindisp and not ndc
     cfg = oracle.RenderConfig(variant="object", n_samples=s, n_importance=n_imp, white_bkgd=white, lindisp=lindisp)
-    rays = mg.chair_rays(H_ref, n, 1000 + idx)
+    rays = mg.llff_rays(H_ref, n, idx % 8)[0] if ndc else mg.chair_rays(H_ref, n, 1000 + idx)
     embed, ch = H_ref.get_embedder(10, 0)
     embed_d, ch_d = H_ref.get_embedder(4, 0)
     torch.manual_seed(idx)
@@ -48,9 +53,10 @@ def object_case(run_nerf, H_ref, rng, idx):
     extra = {}
     if train:
         g = torch.Generator().manual_seed(77 + idx)
-        extra = dict(t_rand=torch.rand(n, s, generator=g), noise_coarse=torch.rand(n, s, generator=g))
+        draw = torch.randn if gauss else torch.rand
+        extra = dict(t_rand=torch.rand(n, s, generator=g), noise_coarse=draw(n, s, generator=g))
         if n_imp > 0:
-            extra.update(u=torch.rand(n, n_imp, generator=g), noise_fine=torch.rand(n, s + n_imp, generator=g))
+            extra.update(u=torch.rand(n, n_imp, generator=g), noise_fine=draw(n, s + n_imp, generator=g))
     feed = [extra[k] for k in ("t_rand", "noise_coarse", "u", "noise_fine") if k in extra]
     with torch.no_grad(), mg.injected_rng(np_rand=feed):
         ref = run_nerf.render_rays(rays, net_c, q, s, retraw=True, lindisp=lindisp, perturb=1.0 if train else 0.0,
@@ -62,7 +68,8 @@ def object_case(run_nerf, H_ref, rng, idx):
     if n_imp > 0:
         pairs += [(k + "0", k + "_coarse") for k in ("rgb", "disp", "acc", "albedo", "shading", "residual")] + [("z_std", "z_std")]
     worst = max(mg.check_same(f"object#{idx}/{rk}", ref[rk], mine[ok]) for rk, ok in pairs)
-    return f"object n={n} S={s}+{n_imp} white={white:d} lindisp={lindisp:d} train={train:d}: {worst:.1e}"
+    return (f"object n={n} S={s}+{n_imp} {'ndc' if ndc else 'chair'} white={white:d} lindisp={lindisp:d} train={train:d}"
+            f"{' noise=' + ('randn' if gauss else 'rand') if train else ''}: {worst:.1e}")
 
 
 def ssr_case(SSRTrainer, ssr_rays, rng, idx):

@@ -4,7 +4,7 @@
 Runs only in the build container (``/root/reference`` is mounted there, read-only); the GPU box
 never sees the reference, only the ``*.npz`` fixtures this script writes.  Usage::
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [case names]
 
 For every case the script
   1. builds the reference modules (``object_level/run_nerf_helpers.NeRF`` or
@@ -118,6 +118,40 @@ def chair_rays(H_ref, n, seed, near=2.0, far=6.0):
     return torch.cat([ro, rd, near * torch.ones_like(rd[:, :1]), far * torch.ones_like(rd[:, :1]), vd], -1)
 
 
+# LLFF forward-facing camera: fern at factor 8 (504 x 378, focal ~407.6 px: ~63.5 deg across the width)
+LLFF_H, LLFF_W, LLFF_FOCAL = 378, 504, 407.5658
+
+
+def llff_camera(seed, H=LLFF_H, W=LLFF_W):
+    """(H, W, K, c2w) of an LLFF-like view: fern's field of view at any resolution (the focal scales with W), and a pose
+    near the identity as LLFF's recentred spiral poses are (a few degrees of rotation, a few hundredths of translation)."""
+    focal = LLFF_FOCAL * W / LLFF_W
+    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
+    ax, ay = np.deg2rad(-2.0 + 0.5 * seed), np.deg2rad(3.0 - 0.5 * seed)
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    c2w = np.concatenate([ry @ rx, np.array([[0.08 - 0.01 * seed], [-0.05 + 0.01 * seed], [0.03]])], 1)
+    return H, W, K, torch.tensor(c2w, dtype=torch.float32)
+
+
+def llff_frame_rays(H_ref, H, W, K, c2w):
+    """Every ray of an LLFF frame as the reference's render() assembles it for ``ndc=True`` (run_nerf.py:100-125): get_rays,
+    view directions from the WORLD-space rays_d, then ndc_rays(H, W, focal, 1.) and near = 0, far = 1."""
+    ro, rd = H_ref.get_rays(H, W, K, c2w)
+    vd = rd / torch.norm(rd, dim=-1, keepdim=True)
+    ro, rd = H_ref.ndc_rays(H, W, K[0][0], 1., ro, rd)
+    ro, rd, vd = ro.reshape(-1, 3).float(), rd.reshape(-1, 3).float(), vd.reshape(-1, 3).float()
+    return torch.cat([ro, rd, torch.zeros_like(rd[:, :1]), torch.ones_like(rd[:, :1]), vd], -1).contiguous()
+
+
+def llff_rays(H_ref, n, seed):
+    """n NDC rays of the fern-sized LLFF camera (random pixels of the whole frame); also returns the camera."""
+    H, W, K, c2w = llff_camera(seed)
+    rays = llff_frame_rays(H_ref, H, W, K, c2w)
+    rng = np.random.RandomState(3000 + seed)
+    return rays[torch.from_numpy(rng.choice(H * W, n, replace=False))].contiguous(), dict(H=H, W=W, K=K, c2w=c2w)
+
+
 def room_rays(ssr_rays, n, seed, near=0.1, far=10.0):
     import contextlib, io
     T = torch.eye(4)[None].clone()
@@ -211,10 +245,17 @@ def keep_well_conditioned(name, rays, n, sd_c, sd_f, cfg, t_vals, draw_extra):
 # object-level cases
 # ------------------------------------------------------------------------------------------
 def object_case(run_nerf, H_ref, name, n, seed, n_importance, white_bkgd, lindisp, train_rng,
-                sigma_gain_log2, quantile, weight_gain_log2=0, keep_raw=4):
+                sigma_gain_log2, quantile, weight_gain_log2=0, keep_raw=4, camera="chair", noise="uniform"):
+    """``camera``: "chair" (synthetic 800x800, near 2, far 6) or "llff" (NDC rays of a fern-sized forward-facing view, near 0,
+    far 1; H, W, K and c2w are stored).  ``noise``: the distribution of the raw noise fed in training mode - "uniform" in
+    [0, 1) or "gaussian" (standard normal, as the reference's torch.randn draws it: about half of it negative)."""
     cfg = oracle.RenderConfig(variant="object", n_samples=64, n_importance=n_importance,
                               white_bkgd=white_bkgd, lindisp=lindisp)
-    cand = chair_rays(H_ref, 6 * n, seed)
+    cam = {}
+    if camera == "llff":
+        cand, cam = llff_rays(H_ref, 6 * n, seed)
+    else:
+        cand = chair_rays(H_ref, 6 * n, seed)
     sd_c, b_c = calibrated_weights("object", 0, 2 * seed, cand, cfg, sigma_gain_log2, weight_gain_log2, quantile)
     sd_f, b_f = calibrated_weights("object", 0, 2 * seed + 1, cand, cfg, sigma_gain_log2, weight_gain_log2, quantile)
     wp = dict(sigma_gain_log2=sigma_gain_log2, weight_gain_log2=weight_gain_log2, sigma_bias_coarse=b_c, sigma_bias_fine=b_f)
@@ -225,9 +266,10 @@ def object_case(run_nerf, H_ref, name, n, seed, n_importance, white_bkgd, lindis
         if not train_rng:
             return {}
         g = torch.Generator().manual_seed(500 + seed)
-        ex = dict(t_rand=torch.rand(m, 64, generator=g), noise_coarse=torch.rand(m, 64, generator=g) * std)
+        draw = torch.randn if noise == "gaussian" else torch.rand
+        ex = dict(t_rand=torch.rand(m, 64, generator=g), noise_coarse=draw(m, 64, generator=g) * std)
         if n_importance > 0:
-            ex.update(u=torch.rand(m, n_importance, generator=g), noise_fine=torch.rand(m, 64 + n_importance, generator=g) * std)
+            ex.update(u=torch.rand(m, n_importance, generator=g), noise_fine=draw(m, 64 + n_importance, generator=g) * std)
         return ex
 
     rays, extra = keep_well_conditioned(name, cand, n, sd_c, sd_f, cfg, t_vals, draw_extra)
@@ -238,7 +280,8 @@ def object_case(run_nerf, H_ref, name, n, seed, n_importance, white_bkgd, lindis
     net_c.load_state_dict(sd_c); net_f.load_state_dict(sd_f)
     q = lambda x, v, fn: run_nerf.run_network(x, v, fn, embed_fn=embed, embeddirs_fn=embed_d, netchunk=65536)
     # the reference's pytest hooks call np.random.rand once per draw (run_nerf.py:389-393,480-484; helpers:416-425),
-    # in this order: t_rand, coarse noise, u, fine noise
+    # in this order: t_rand, coarse noise, u, fine noise (Gaussian noise goes through the same hook: it multiplies what
+    # np.random.rand returns by raw_noise_std = 1, exactly)
     feed = [extra[k] for k in ("t_rand", "noise_coarse", "u", "noise_fine") if k in extra]
     with torch.no_grad(), injected_rng(np_rand=feed):
         ref = run_nerf.render_rays(rays, net_c, q, 64, retraw=True, lindisp=lindisp,
@@ -260,7 +303,9 @@ def object_case(run_nerf, H_ref, name, n, seed, n_importance, white_bkgd, lindis
           f"[{float(mine['acc_' + suffix].min()):.3f}, {float(mine['acc_' + suffix].max()):.3f}]")
     fx = dict(variant="object", seed=seed, **wp,
               n_importance=n_importance, white_bkgd=white_bkgd, lindisp=lindisp, n_classes=0, endpoint_feat=False,
-              rays=rays, t_vals=t_vals)
+              rays=rays, t_vals=t_vals, **cam)
+    if camera == "llff":
+        fx.update(ndc=True, noise=noise)
     fx.update({"in_" + k: v for k, v in extra.items()})
     for rk, ok in pairs:                       # reference outputs under stage-neutral names
         v = ref[rk]
@@ -429,36 +474,55 @@ def stage_sample_pdf_cases(H_ref, ssr_rays):
     print("stage_sample_pdf: oracle == reference")
 
 
-def main():
+def main(only=()):
+    """Every fixture of this script; ``only`` (command-line names) regenerates just those - the zip containers carry write
+    times, so rewriting a fixture whose data did not change still changes its bytes."""
     run_nerf, H_ref, SSRTrainer, ssr_rays, ssr_mu = import_reference()
-    # ---- object-level: BASELINE configs 1-3 in miniature
-    object_case(run_nerf, H_ref, "object_chair_det", n=24, seed=0, n_importance=128, white_bkgd=True,
-                lindisp=False, train_rng=False, sigma_gain_log2=5, quantile=0.7)
-    object_case(run_nerf, H_ref, "object_chair_dense", n=12, seed=1, n_importance=128, white_bkgd=True,
-                lindisp=False, train_rng=False, sigma_gain_log2=5, quantile=0.1)
-    object_case(run_nerf, H_ref, "object_chair_train_rng", n=12, seed=2, n_importance=128, white_bkgd=True,
-                lindisp=False, train_rng=True, sigma_gain_log2=5, quantile=0.5)
-    object_case(run_nerf, H_ref, "object_coarse_only_lindisp", n=12, seed=3, n_importance=0, white_bkgd=False,
-                lindisp=True, train_rng=False, sigma_gain_log2=5, quantile=0.5)
-    object_case(run_nerf, H_ref, "object_strong_weights", n=8, seed=4, n_importance=128, white_bkgd=False,
-                lindisp=False, train_rng=False, sigma_gain_log2=3, quantile=0.5, weight_gain_log2=1)
-    object_case(run_nerf, H_ref, "object_empty_space", n=8, seed=5, n_importance=128, white_bkgd=True,
-                lindisp=False, train_rng=False, sigma_gain_log2=3, quantile=2.0)   # sigma < 0 everywhere: acc = 0, disp NaN
-    # ---- SSR: BASELINE config 4 in miniature
-    ssr_case(SSRTrainer, ssr_rays, "ssr_room_det_c28", n=24, seed=0, n_classes=28, endpoint_feat=False,
-             white_bkgd=False, training=False, sigma_gain_log2=4, quantile=0.7)
-    ssr_case(SSRTrainer, ssr_rays, "ssr_room_train_rng_c28", n=12, seed=1, n_classes=28, endpoint_feat=False,
-             white_bkgd=False, training=True, sigma_gain_log2=4, quantile=0.5)
-    ssr_case(SSRTrainer, ssr_rays, "ssr_endpoint_c5_wb", n=8, seed=2, n_classes=5, endpoint_feat=True,
-             white_bkgd=True, training=False, sigma_gain_log2=4, quantile=0.5)
-    ssr_case(SSRTrainer, ssr_rays, "ssr_c101", n=6, seed=3, n_classes=101, endpoint_feat=False,
-             white_bkgd=False, training=False, sigma_gain_log2=4, quantile=0.3)
-    ssr_case(SSRTrainer, ssr_rays, "ssr_c1", n=6, seed=4, n_classes=1, endpoint_feat=False,
-             white_bkgd=False, training=False, sigma_gain_log2=3, quantile=0.5)
-    # ---- stage-level edge cases
-    stage_composite_cases(run_nerf, ssr_mu)
-    stage_sample_pdf_cases(H_ref, ssr_rays)
+    obj = lambda name, **kw: (name, lambda: object_case(run_nerf, H_ref, name, **kw))
+    ssr = lambda name, **kw: (name, lambda: ssr_case(SSRTrainer, ssr_rays, name, **kw))
+    cases = [
+        # ---- object-level: BASELINE configs 1-3 in miniature
+        obj("object_chair_det", n=24, seed=0, n_importance=128, white_bkgd=True, lindisp=False, train_rng=False,
+            sigma_gain_log2=5, quantile=0.7),
+        obj("object_chair_dense", n=12, seed=1, n_importance=128, white_bkgd=True, lindisp=False, train_rng=False,
+            sigma_gain_log2=5, quantile=0.1),
+        obj("object_chair_train_rng", n=12, seed=2, n_importance=128, white_bkgd=True, lindisp=False, train_rng=True,
+            sigma_gain_log2=5, quantile=0.5),
+        obj("object_coarse_only_lindisp", n=12, seed=3, n_importance=0, white_bkgd=False, lindisp=True, train_rng=False,
+            sigma_gain_log2=5, quantile=0.5),
+        obj("object_strong_weights", n=8, seed=4, n_importance=128, white_bkgd=False, lindisp=False, train_rng=False,
+            sigma_gain_log2=3, quantile=0.5, weight_gain_log2=1),
+        obj("object_empty_space", n=8, seed=5, n_importance=128, white_bkgd=True, lindisp=False, train_rng=False,
+            sigma_gain_log2=3, quantile=2.0),   # sigma < 0 everywhere: acc = 0, disp NaN
+        # ---- object-level, the LLFF configs' call shape (fern, flower, ... trex): NDC rays, near 0, far 1, 64 + 64 samples,
+        # no white background; in training raw_noise_std = 1 drawn by torch.randn (run_nerf.py:386-387).  Density calibration
+        # chosen so that the kept rays are neither all empty nor all opaque: without noise the chair-case gain (2^5, quantile
+        # 0.5) leaves every fine acc at 0 or 1 on NDC rays; 2^4 with weight gain 2 puts 2/3 of them strictly in between
+        obj("object_llff_det", n=16, seed=6, n_importance=64, white_bkgd=False, lindisp=False, train_rng=False,
+            sigma_gain_log2=4, quantile=0.5, weight_gain_log2=1, camera="llff"),
+        obj("object_llff_train_gaussian", n=12, seed=7, n_importance=64, white_bkgd=False, lindisp=False, train_rng=True,
+            sigma_gain_log2=5, quantile=0.5, camera="llff", noise="gaussian"),
+        # ---- SSR: BASELINE config 4 in miniature
+        ssr("ssr_room_det_c28", n=24, seed=0, n_classes=28, endpoint_feat=False, white_bkgd=False, training=False,
+            sigma_gain_log2=4, quantile=0.7),
+        ssr("ssr_room_train_rng_c28", n=12, seed=1, n_classes=28, endpoint_feat=False, white_bkgd=False, training=True,
+            sigma_gain_log2=4, quantile=0.5),
+        ssr("ssr_endpoint_c5_wb", n=8, seed=2, n_classes=5, endpoint_feat=True, white_bkgd=True, training=False,
+            sigma_gain_log2=4, quantile=0.5),
+        ssr("ssr_c101", n=6, seed=3, n_classes=101, endpoint_feat=False, white_bkgd=False, training=False,
+            sigma_gain_log2=4, quantile=0.3),
+        ssr("ssr_c1", n=6, seed=4, n_classes=1, endpoint_feat=False, white_bkgd=False, training=False,
+            sigma_gain_log2=3, quantile=0.5),
+        # ---- stage-level edge cases
+        ("stage_composite", lambda: stage_composite_cases(run_nerf, ssr_mu)),
+        ("stage_sample_pdf", lambda: stage_sample_pdf_cases(H_ref, ssr_rays)),
+    ]
+    unknown = set(only) - {name for name, _ in cases}
+    assert not unknown, f"no such case: {sorted(unknown)}"
+    for name, run in cases:
+        if not only or name in only:
+            run()
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden GRADIENT vectors, produced by the reference's own autograd (build container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grad.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grad.py [case names]
 
 Companion of make_golden.py (same import recipe, same rules: the reference is imported from /root/reference,
 never copied; only inputs and reference outputs are stored).  What the trainers do with the path is
@@ -12,6 +12,8 @@ REFERENCE's autograd returns for them:
   grad_composite_{object,ssr}_wb{0,1}.npz   raw2outputs alone: d loss / d raw                (stage boundary)
   grad_render_object.npz                    render_rays, coarse + fine: d loss / d every network parameter,
                                             stored as digests (norm, leading entries, a seeded projection)
+  grad_render_object_llff.npz               the same for a training step of the LLFF shape: NDC rays, 64 + 64 samples,
+                                            perturb = 1, Gaussian raw noise (std 1), the draws stored as in_*
 
 and asserts that autograd through the CPU oracle (oracle/intrinsic_render.py) gives the same numbers, so the
 oracle's backward is pinned like its forward.
@@ -30,7 +32,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE)))
 
 import make_golden as mg  # noqa: E402
 import oracle  # noqa: E402
-from _cases import case_config, case_weights  # noqa: E402
+from _cases import case_config, case_random_inputs, case_weights  # noqa: E402
 from conftest import load_golden  # noqa: E402
 
 DIGEST_HEAD = 16
@@ -110,21 +112,28 @@ def composite_cases(run_nerf, ssr_mu):
     print("grad_composite_*: oracle autograd == reference autograd")
 
 
-def render_case(run_nerf, H_ref):
-    """Parameter gradients of the whole object-level path (training-step shape: coarse + fine nets, white background),
-    on the rays of an existing forward fixture."""
-    fx = load_golden("object_chair_det")
+def render_case(run_nerf, H_ref, name="grad_render_object", source="object_chair_det"):
+    """Parameter gradients of the whole object-level path (training-step shape: coarse + fine nets), on the first 8 rays of an
+    existing forward fixture, with that fixture's configuration.  A fixture with training draws (``in_*``: perturbed depths,
+    raw noise, random u) is replayed through the reference's pytest hooks, in its draw order; the draws of the 8 rays are
+    stored with the gradients."""
+    fx = load_golden(source)
     cfg = case_config(fx)
     sd_c, sd_f = case_weights(fx)
     rays = torch.from_numpy(fx["rays"])[:8].contiguous()
+    extra = {k: v[:8].contiguous() for k, v in case_random_inputs(fx).items()}
+    train = "t_rand" in extra
     embed, ch = H_ref.get_embedder(10, 0)
     embed_d, ch_d = H_ref.get_embedder(4, 0)
     mk = lambda: H_ref.NeRF(D=8, W=256, input_ch=ch, output_ch=5, skips=[4], input_ch_views=ch_d, use_viewdirs=True)
     net_c, net_f = mk(), mk()
     net_c.load_state_dict(sd_c); net_f.load_state_dict(sd_f)
     q = lambda x, v, fn: run_nerf.run_network(x, v, fn, embed_fn=embed, embeddirs_fn=embed_d, netchunk=65536)
-    ref = run_nerf.render_rays(rays, net_c, q, 64, retraw=True, lindisp=False, perturb=0.0, N_importance=128,
-                               network_fine=net_f, white_bkgd=True, raw_noise_std=0.0)
+    feed = [extra[k] for k in ("t_rand", "noise_coarse", "u", "noise_fine") if k in extra]
+    with mg.injected_rng(np_rand=feed):
+        ref = run_nerf.render_rays(rays, net_c, q, 64, retraw=True, lindisp=cfg.lindisp, perturb=1.0 if train else 0.0,
+                                   N_importance=cfg.n_importance, network_fine=net_f, white_bkgd=cfg.white_bkgd,
+                                   raw_noise_std=1.0 if train else 0.0, pytest=train)
     # the maps the training loss reads (run_nerf.py:976-1008): fine and coarse rgb / albedo / shading / residual, disp, acc
     keys = ["rgb_map", "albedo_map", "shading_map", "residual_map", "disp_map", "acc_map",
             "rgb0", "albedo0", "shading0", "residual0", "acc0"]
@@ -134,30 +143,42 @@ def render_case(run_nerf, H_ref):
     # oracle autograd on the same thing
     pc = {k: v.clone().requires_grad_(True) for k, v in sd_c.items()}
     pf = {k: v.clone().requires_grad_(True) for k, v in sd_f.items()}
-    mine = oracle.render_rays(rays, pc, pf, cfg, t_vals=torch.from_numpy(fx["t_vals"]))
+    mine = oracle.render_rays(rays, pc, pf, cfg, t_vals=torch.from_numpy(fx["t_vals"]), **extra)
     name_of = {"rgb_map": "rgb_fine", "albedo_map": "albedo_fine", "shading_map": "shading_fine", "residual_map": "residual_fine",
                "disp_map": "disp_fine", "acc_map": "acc_fine", "rgb0": "rgb_coarse", "albedo0": "albedo_coarse",
                "shading0": "shading_coarse", "residual0": "residual_coarse", "acc0": "acc_coarse"}
     sum((cot[k] * mine[name_of[k]]).sum() for k in keys).backward()
-    out = dict(rays=rays, n_rays=8, **{"cot_" + name_of[k]: v for k, v in cot.items()})
+    out = dict(rays=rays, n_rays=8, **{"cot_" + name_of[k]: v for k, v in cot.items()}, **{"in_" + k: v for k, v in extra.items()})
     worst = 0.0
     for tag, net, params in (("coarse", net_c, pc), ("fine", net_f, pf)):
-        for i, (name, p) in enumerate(net.named_parameters()):
-            assert p.grad is not None, name
+        for i, (pname, p) in enumerate(net.named_parameters()):
+            assert p.grad is not None, pname
             gn = float(p.grad.double().norm())
-            dev = float((p.grad.double() - params[name].grad.double()).norm()) / max(gn, 1e-30)
+            dev = float((p.grad.double() - params[pname].grad.double()).norm()) / max(gn, 1e-30)
             worst = max(worst, dev)
-            out[f"grad_{tag}/{name}"] = digest(p.grad, 1000 + i)
+            out[f"grad_{tag}/{pname}"] = digest(p.grad, 1000 + i)
     assert worst <= 1e-5, f"oracle autograd deviates from the reference's by {worst:.2e} (relative, per tensor)"
-    print(f"grad_render_object: oracle autograd == reference autograd (worst per-tensor relative deviation {worst:.1e})")
-    mg.save("grad_render_object", source_fixture="object_chair_det", **out)
+    print(f"{name}: oracle autograd == reference autograd (worst per-tensor relative deviation {worst:.1e})")
+    mg.save(name, source_fixture=source, **out)
 
 
-def main():
+def main(only=()):
+    """Every fixture of this script, or only the ones named on the command line (rewriting an unchanged fixture changes its
+    bytes: the zip container records write times)."""
     run_nerf, H_ref, SSRTrainer, ssr_rays, ssr_mu = mg.import_reference()
-    composite_cases(run_nerf, ssr_mu)
-    render_case(run_nerf, H_ref)
+    cases = [
+        ("grad_composite", lambda: composite_cases(run_nerf, ssr_mu)),
+        ("grad_render_object", lambda: render_case(run_nerf, H_ref)),
+        # a training step of the LLFF configs: NDC rays, 64 + 64 samples, perturb = 1, raw_noise_std = 1 with Gaussian
+        # (partly negative) noise, no white background
+        ("grad_render_object_llff", lambda: render_case(run_nerf, H_ref, "grad_render_object_llff", "object_llff_train_gaussian")),
+    ]
+    unknown = set(only) - {name for name, _ in cases}
+    assert not unknown, f"no such case: {sorted(unknown)}"
+    for name, run in cases:
+        if not only or name in only:
+            run()
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

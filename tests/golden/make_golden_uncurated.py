@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """UN-CURATED golden fixtures: the REAL reference on unfiltered rays with default-``nn.Linear``-init networks.
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_uncurated.py        (build container only)
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_uncurated.py [case names]       (build container only)
 
 The fixtures of ``make_golden.py`` use 1/f-spectrum weights and keep only rays on which the reference arithmetic
 reproduces itself (fp32 vs fp64) - VERDICT r01 asked for the opposite as well.  Here nothing is selected:
@@ -23,7 +23,9 @@ reproduces itself (fp32 vs fp64) - VERDICT r01 asked for the opposite as well.  
 
 Cases: ``uncurated_object_coarse_only_wb`` (BASELINE configs[1] in miniature: 64 coarse samples, coarse network
 only, white background - the only coarse-only fixture of make_golden.py has lindisp and no white background),
-``uncurated_object_chair_wb`` (configs[2]), ``uncurated_ssr_room_c28`` (configs[3]).
+``uncurated_object_chair_wb`` (configs[2]), ``uncurated_ssr_room_c28`` (configs[3]), ``uncurated_object_llff_ndc`` (the call
+shape of the reference's ten LLFF configs: every ray of a 16 x 12 fern-sized frame in NDC, near 0, far 1, 64 + 64 samples,
+no white background; H, W, K and c2w are stored so that a test can render the same frame through ``render(ndc=True)``).
 """
 import contextlib
 import io
@@ -132,9 +134,12 @@ def fine_hazard(fx, rays, sd_f, cfg, mine, m64, pairs):
     return cal.fine_pass_hazard(rays, sd_f, cfg, mine, m64, subset=score <= 0.2)
 
 
-def object_case(run_nerf, H_ref, name, n, n_importance, raw_every=4):
-    rays = frame_rays_object(H_ref, n)
-    cfg = oracle.RenderConfig(variant="object", n_samples=64, n_importance=n_importance, white_bkgd=True)
+def object_case(run_nerf, H_ref, name, n, n_importance, raw_every=4, rays=None, white_bkgd=True, camera=None):
+    """``rays``: the case's ray batch (default: every k-th ray of the chair frame); ``camera``: dict of H, W, K, c2w to store
+    with it (a whole LLFF frame)."""
+    rays = frame_rays_object(H_ref, n) if rays is None else rays
+    n = rays.shape[0]
+    cfg = oracle.RenderConfig(variant="object", n_samples=64, n_importance=n_importance, white_bkgd=white_bkgd)
     sd_c, sd_f = cal.calibrated_default_init("object", 0, 0, rays), cal.calibrated_default_init("object", 0, 1, rays)
     embed, ch = H_ref.get_embedder(10, 0)
     embed_d, ch_d = H_ref.get_embedder(4, 0)
@@ -145,7 +150,7 @@ def object_case(run_nerf, H_ref, name, n, n_importance, raw_every=4):
     with torch.no_grad():
         with captured_stages(run_nerf) as cap:
             ref = run_nerf.render_rays(rays, net_c, q, 64, retraw=False, perturb=0.0, N_importance=n_importance,
-                                       network_fine=net_f if n_importance > 0 else None, white_bkgd=True, raw_noise_std=0.0)
+                                       network_fine=net_f if n_importance > 0 else None, white_bkgd=white_bkgd, raw_noise_std=0.0)
         mine = oracle.render_rays(rays, sd_c, sd_f if n_importance > 0 else None, cfg, stages=True)
         m64 = oracle.render_rays(rays.double(), to64(sd_c), to64(sd_f) if n_importance > 0 else None, cfg, stages=True)
     lvl = "fine" if n_importance > 0 else "coarse"
@@ -159,8 +164,8 @@ def object_case(run_nerf, H_ref, name, n, n_importance, raw_every=4):
     base = oracle.make_state_dict("object", 0, seed=0)
     gc, bc = head_calibration(sd_c, base)
     gf, bf = head_calibration(sd_f, oracle.make_state_dict("object", 0, seed=1))
-    fx = dict(variant="object", n_classes=0, n_importance=n_importance, white_bkgd=True, seed_coarse=0, seed_fine=1,
-              alpha_gain_coarse=gc, alpha_bias_coarse=bc, alpha_gain_fine=gf, alpha_bias_fine=bf, rays=rays)
+    fx = dict(variant="object", n_classes=0, n_importance=n_importance, white_bkgd=white_bkgd, seed_coarse=0, seed_fine=1,
+              alpha_gain_coarse=gc, alpha_bias_coarse=bc, alpha_gain_fine=gf, alpha_bias_fine=bf, rays=rays, **(camera or {}))
     for rk, ok in pairs:
         fx["ref_" + ok] = ref[rk]
         fx["f64_" + ok] = m64[ok]
@@ -208,12 +213,37 @@ def ssr_case(SSRTrainer, ssr_rays, name, n, n_classes, raw_every=8):
     mg.save(name, **fx)
 
 
-def main():
+def llff_frame(H_ref, H=12, W=16):
+    """EVERY ray of a small LLFF frame (fern's field of view, focal scaled to W), through the reference's own get_rays ->
+    ndc_rays, near 0, far 1 (make_golden.llff_frame_rays)."""
+    H, W, K, c2w = mg.llff_camera(0, H, W)
+    return mg.llff_frame_rays(H_ref, H, W, K, c2w), dict(H=H, W=W, K=K, c2w=c2w, ndc=True)
+
+
+def main(only=()):
+    """Every fixture of this script, or only the ones named on the command line (rewriting an unchanged fixture changes its
+    bytes: the zip container records write times)."""
     run_nerf, H_ref, SSRTrainer, ssr_rays, _ = mg.import_reference()
-    object_case(run_nerf, H_ref, "uncurated_object_coarse_only_wb", n=256, n_importance=0)
-    object_case(run_nerf, H_ref, "uncurated_object_chair_wb", n=512, n_importance=128)
-    ssr_case(SSRTrainer, ssr_rays, "uncurated_ssr_room_c28", n=512, n_classes=28)
+
+    def llff(name):
+        rays, camera = llff_frame(H_ref)
+        object_case(run_nerf, H_ref, name, n=None, n_importance=64, raw_every=8, rays=rays, white_bkgd=False,
+                    camera=camera)
+
+    cases = [
+        ("uncurated_object_coarse_only_wb", lambda name: object_case(run_nerf, H_ref, name, n=256, n_importance=0)),
+        ("uncurated_object_chair_wb", lambda name: object_case(run_nerf, H_ref, name, n=512, n_importance=128)),
+        ("uncurated_ssr_room_c28", lambda name: ssr_case(SSRTrainer, ssr_rays, name, n=512, n_classes=28)),
+        # the LLFF configs' shape (NDC rays, near 0, far 1, 64 + 64 samples, no white background) on a whole 16 x 12 frame
+        # (raw of every 8th ray: the fixture stays under 0.4 MB)
+        ("uncurated_object_llff_ndc", llff),
+    ]
+    unknown = set(only) - {name for name, _ in cases}
+    assert not unknown, f"no such case: {sorted(unknown)}"
+    for name, run in cases:
+        if not only or name in only:
+            run(name)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

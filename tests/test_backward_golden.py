@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import oracle
-from _cases import assert_maps_close, case_config, case_weights
+from _cases import assert_maps_close, case_config, case_random_inputs, case_weights, injected_np_rand
 from conftest import golden_names, load_golden
 
 OBJ_KEYS = ["rgb", "disp", "acc", "weights", "depth", "albedo", "shading", "residual"]
@@ -48,13 +48,26 @@ def test_oracle_autograd_matches_reference(name):
 
 def test_oracle_parameter_gradients_match_reference():
     """Whole path, both networks: digests (norm, projection, leading entries) of every parameter gradient."""
-    fx = load_golden("grad_render_object")
+    _check_oracle_parameter_gradients("grad_render_object")
+
+
+def test_oracle_parameter_gradients_match_reference_noisy_ndc_step():
+    """The same for a training step of the LLFF configs (grad_render_object_llff): NDC rays, 64 + 64 samples, perturbed
+    depths, random u and Gaussian raw noise - about half of it negative - replayed from the fixture."""
+    fx = load_golden("grad_render_object_llff")
+    assert (fx["in_noise_coarse"] < 0).any() and (fx["in_noise_fine"] < 0).any() and float(fx["rays"][:, 6].max()) == 0.0
+    _check_oracle_parameter_gradients("grad_render_object_llff")
+
+
+def _check_oracle_parameter_gradients(name):
+    fx = load_golden(name)
     src = load_golden(str(fx["source_fixture"]))
     cfg = case_config(src)
     sd_c, sd_f = case_weights(src)
     pc = {k: v.clone().requires_grad_(True) for k, v in sd_c.items()}
     pf = {k: v.clone().requires_grad_(True) for k, v in sd_f.items()}
-    out = oracle.render_rays(torch.from_numpy(fx["rays"]), pc, pf, cfg, t_vals=torch.from_numpy(src["t_vals"]))
+    out = oracle.render_rays(torch.from_numpy(fx["rays"]), pc, pf, cfg, t_vals=torch.from_numpy(src["t_vals"]),
+                             **case_random_inputs(fx))
     loss = sum((torch.from_numpy(fx[k]) * out[k[4:]]).sum() for k in fx if k.startswith("cot_"))
     loss.backward()
     checked = 0
@@ -143,11 +156,18 @@ def test_training_step_gradients_vs_reference():
     rays = torch.from_numpy(fx["rays"]).to(dev)
     ret = ol.render_rays(rays, net_c, ol.NetworkQuery(embed, embed_d), 64, retraw=True, N_importance=128, network_fine=net_f,
                          white_bkgd=True)
-    name_of = {"rgb_fine": "rgb_map", "albedo_fine": "albedo_map", "shading_fine": "shading_map", "residual_fine": "residual_map",
-               "disp_fine": "disp_map", "acc_fine": "acc_map", "rgb_coarse": "rgb0", "albedo_coarse": "albedo0",
-               "shading_coarse": "shading0", "residual_coarse": "residual0", "acc_coarse": "acc0"}
-    loss = sum((torch.from_numpy(fx["cot_" + k]).to(dev) * ret[name_of[k]]).sum() for k in name_of)
+    loss = sum((torch.from_numpy(fx["cot_" + k]).to(dev) * ret[_NAME_OF[k]]).sum() for k in _NAME_OF)
     loss.backward()
+    _assert_gradient_digests(fx, net_c, net_f)
+
+
+_NAME_OF = {"rgb_fine": "rgb_map", "albedo_fine": "albedo_map", "shading_fine": "shading_map", "residual_fine": "residual_map",
+            "disp_fine": "disp_map", "acc_fine": "acc_map", "rgb_coarse": "rgb0", "albedo_coarse": "albedo0",
+            "shading_coarse": "shading0", "residual_coarse": "residual0", "acc_coarse": "acc0"}
+
+
+def _assert_gradient_digests(fx, net_c, net_f):
+    checked = 0
     for tag, net in (("coarse", net_c), ("fine", net_f)):
         for i, (name, p) in enumerate(net.named_parameters()):
             want = fx[f"grad_{tag}/{name}"]
@@ -157,6 +177,46 @@ def test_training_step_gradients_vs_reference():
             assert abs(got[0] - want[0]) <= 1e-4 * want[0], (tag, name, got[0], want[0])
             assert abs(got[1] - want[1]) <= 1e-4 * want[0] * np.sqrt(p.numel()), (tag, name)
             np.testing.assert_allclose(got[2:], want[2:], rtol=1e-3, atol=1e-4 * want[0], err_msg=f"{tag}/{name}")
+            checked += 1
+    assert checked == sum(1 for k in fx if k.startswith("grad_"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mlp", ["hip", "torch"])
+def test_noisy_ndc_training_step_gradients_vs_reference(mlp, monkeypatch):
+    """A training step of the LLFF configs through the object-level front-end: NDC rays (near 0, far 1), 64 + 64 samples,
+    perturb = 1 and raw_noise_std = 1 with Gaussian noise - negative about half the time - fed in the reference's draw order
+    through its pytest hooks (t_rand, coarse noise, u, fine noise).  The staged path saves that noise for the compositing
+    backward (kernels._CompositeFn); every parameter gradient of both networks against the reference's autograd
+    (grad_render_object_llff.npz), with the network backward on the HIP kernels (default) and on torch's layers
+    (INERF_TRAIN_MLP=torch)."""
+    import warnings
+    from intrinsicnerf_amd import object_level as ol
+    if mlp == "torch":
+        monkeypatch.setenv("INERF_TRAIN_MLP", "torch")
+    else:
+        monkeypatch.delenv("INERF_TRAIN_MLP", raising=False)
+    dev = torch.device("cuda:0")
+    fx = load_golden("grad_render_object_llff")
+    src = load_golden(str(fx["source_fixture"]))
+    cfg = case_config(src)
+    assert cfg.n_importance == 64 and not cfg.white_bkgd
+    sd_c, sd_f = case_weights(src)
+    embed, ch = ol.get_embedder(10, 0); embed_d, ch_d = ol.get_embedder(4, 0)
+    mk = lambda: ol.NeRF(D=8, W=256, input_ch=ch, output_ch=5, skips=[4], input_ch_views=ch_d, use_viewdirs=True).to(dev)
+    net_c, net_f = mk(), mk()
+    net_c.load_state_dict(sd_c); net_f.load_state_dict(sd_f)
+    rays = torch.from_numpy(fx["rays"]).to(dev)
+    rnd = case_random_inputs(fx)
+    assert (rnd["noise_coarse"] < 0).any() and (rnd["noise_fine"] < 0).any()
+    with warnings.catch_warnings(), injected_np_rand([rnd[k] for k in ("t_rand", "noise_coarse", "u", "noise_fine")]):
+        warnings.simplefilter("ignore")
+        ret = ol.render_rays(rays, net_c, ol.NetworkQuery(embed, embed_d), 64, retraw=True, perturb=1., N_importance=64,
+                             network_fine=net_f, white_bkgd=False, raw_noise_std=1., pytest=True)
+    assert tuple(ret["raw"].shape) == (rays.shape[0], 128, 11) and ret["rgb_map"].grad_fn is not None
+    loss = sum((torch.from_numpy(fx["cot_" + k]).to(dev) * ret[_NAME_OF[k]]).sum() for k in _NAME_OF)
+    loss.backward()
+    _assert_gradient_digests(fx, net_c, net_f)
 
 
 @pytest.mark.gpu

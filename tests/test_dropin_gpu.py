@@ -3,6 +3,8 @@ run_nerf.py / trainer.py; these tests do what those scripts the
 
 * ``create_nerf(args)`` with the chair config's values, the ``network_query_fn`` LAMBDA of run_nerf.py:298-301 (not the
   package's NetworkQuery), ``render(H, W, K, chunk=args.chunk, c2w=pose, **render_kwargs_test)`` (run_nerf.py:167-170);
+* the same with an LLFF config's values: NDC rays (near 0, far 1), 64 + 64 samples, raw noise in training, no white
+  background - the eval render of a whole frame against the reference's maps;
 * a ``.tar`` checkpoint with the reference's top-level keys, reloaded the way run_nerf.py:313-330 reloads it;
 * an ``SSRTrainer``-like object configured from the SSR_room0_config.yaml-shaped dict through the reference's
   ``set_params`` attribute names, ``create_ssr()``, a ``.ckpt`` reload (trainer.py:1042-1047) and ``render_rays``.
@@ -15,7 +17,8 @@ import pytest
 import torch
 
 import oracle
-from _cases import assert_maps_close
+from _cases import assert_maps_close, uncurated_judge, uncurated_weights
+from conftest import load_golden
 from oracle import calibration as cal
 
 # INTEGRATION.md, variant A: the reference's scripts import the package's symbols over their own definitions
@@ -52,11 +55,22 @@ def reference_style_create_nerf(args, dev):
                                                                         netchunk=args.netchunk)
     train = {"network_query_fn": network_query_fn, "perturb": args.perturb, "N_importance": args.N_importance,
              "network_fine": model_fine, "N_samples": args.N_samples, "network_fn": model, "use_viewdirs": args.use_viewdirs,
-             "white_bkgd": args.white_bkgd, "raw_noise_std": args.raw_noise_std, "ndc": False, "lindisp": args.lindisp}
+             "white_bkgd": args.white_bkgd, "raw_noise_std": args.raw_noise_std}
+    if args.dataset_type != "llff" or args.no_ndc:      # NDC only for forward-facing data: LLFF keeps render()'s ndc=True
+        train["ndc"] = False
+        train["lindisp"] = args.lindisp
     test = {k: train[k] for k in train}
     test["perturb"] = False
     test["raw_noise_std"] = 0.
     return train, test, model, model_fine
+
+
+def llff_args(**over):
+    """object_level/configs/fern.txt (the shape of all ten LLFF configs) + the config_parser defaults it leaves alone."""
+    a = dict(expname="fern_test", dataset_type="llff", factor=8, llffhold=8, N_rand=1024, N_samples=64, N_importance=64,
+             use_viewdirs=True, raw_noise_std=1e0, white_bkgd=False, half_res=False, no_ndc=False, lrate_decay=250)
+    a.update(over)
+    return chair_args(**a)
 
 
 @pytest.fixture(scope="module")
@@ -133,6 +147,101 @@ def test_run_nerf_call_sites_with_the_reference_lambda(chair_scene, tmp_path):
     img_loss.backward()
     opt.step()
     assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in model_fine.parameters())
+
+
+def test_create_nerf_llff_config_keeps_ndc_and_noise():
+    """create_nerf on the LLFF configs (dataset_type llff, no_ndc unset, N_importance 64, raw_noise_std 1): the train kwargs
+    keep render()'s NDC default (run_nerf.py:346-350 sets ndc only for the other datasets) and the noise, the test kwargs
+    drop the noise - in the reference-style factory and in this package's create_nerf - and a training-mode call as
+    run_nerf.py:942-946 makes it returns raw for 64 + 64 samples with a grad_fn."""
+    import inspect
+    from intrinsicnerf_amd import object_level as ol
+    dev = torch.device("cuda:0")
+    args = llff_args()
+    ndc_default = inspect.signature(ol.render).parameters["ndc"].default
+    train_kw, test_kw, model, model_fine = reference_style_create_nerf(args, dev)
+    own_train, own_test, _ = ol.create_nerf(args, device=dev)
+    for train, test in ((train_kw, test_kw), (own_train, own_test)):
+        assert train.get("ndc", ndc_default) is True and "lindisp" not in train
+        assert train["raw_noise_std"] == 1 and train["perturb"] == 1. and train["N_importance"] == 64 and not train["white_bkgd"]
+        assert test["raw_noise_std"] == 0. and test["perturb"] is False and test.get("ndc", ndc_default) is True
+    H, W, K, pose = _llff_frame()
+    sd_c, sd_f = uncurated_weights(load_golden("uncurated_object_llff_ndc"))
+    model.load_state_dict(sd_c); model_fine.load_state_dict(sd_f)
+    ro, rd = ol.get_rays(H, W, K, pose.to(dev))
+    sel = torch.arange(0, H * W, 7)
+    batch = (ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        out = ol.render(H, W, K, chunk=args.chunk, rays=batch, verbose=False, retraw=True, near=0., far=1., **train_kw)
+    n = sel.numel()
+    assert out[0].grad_fn is not None and tuple(out[0].shape) == (n, 3)
+    assert tuple(out[6]["raw"].shape) == (n, 128, 11) and out[6]["raw"].grad_fn is not None
+    ((out[0] - 0.5) ** 2).mean().backward()
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in model_fine.parameters())
+
+
+def _llff_frame():
+    fx = load_golden("uncurated_object_llff_ndc")
+    return int(fx["H"]), int(fx["W"]), fx["K"], torch.from_numpy(fx["c2w"])
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "f16x3-1wg"])
+def test_llff_frame_through_render_ndc(precision, monkeypatch):
+    """The LLFF configs' eval render, as render_path calls it: render(H, W, K, c2w=pose, ndc=True, near=0., far=1.,
+    **render_kwargs_test) with the reference's query LAMBDA, on the whole 16 x 12 frame of uncurated_object_llff_ndc (the REAL
+    reference's maps for every ray, default-init networks).  Every returned map - coarse ones included - on every ray by the
+    un-curated judgement (rank statistics against the reference's own fp32-vs-fp64 distance, plain tolerance where the
+    reference reproduces itself and on every coarse map); then the same frame bit for bit with a caller's chunk that does
+    not divide it, coalesced (the default) and per chunk (INERF_COALESCE_BYTES=0)."""
+    from intrinsicnerf_amd import object_level as ol
+    monkeypatch.setenv("INERF_PRECISION", precision.split("-")[0])
+    if precision.endswith("-1wg"):
+        monkeypatch.setenv("INERF_F16_KERNEL", "single")
+    else:
+        monkeypatch.delenv("INERF_F16_KERNEL", raising=False)
+    dev = torch.device("cuda:0")
+    fx = load_golden("uncurated_object_llff_ndc")
+    H, W, K, pose = _llff_frame()
+    n = H * W
+    assert n == len(fx["rays"]) and not bool(fx["white_bkgd"]) and int(fx["n_importance"]) == 64
+    args = llff_args()
+    _, test_kw, model, model_fine = reference_style_create_nerf(args, dev)
+    sd_c, sd_f = uncurated_weights(fx)
+    model.load_state_dict(sd_c); model_fine.load_state_dict(sd_f)
+    assert ol._as_network_query(test_kw["network_query_fn"]) is not None          # the lambda is recognised: fused path
+    # the rays render() assembles are the fixture's (world-space view directions, NDC origins / directions, near 0, far 1)
+    ro, rd = ol.get_rays(H, W, K, pose)
+    vd = rd / torch.norm(rd, dim=-1, keepdim=True)
+    ro, rd = ol.ndc_rays(H, W, K[0][0], 1., ro, rd)
+    mine = torch.cat([ro.reshape(n, 3), rd.reshape(n, 3), torch.zeros(n, 1), torch.ones(n, 1), vd.reshape(n, 3)], -1)
+    assert_maps_close(mine.numpy(), fx["rays"], 1e-6, 1e-7, "NDC rays")
+
+    def frame(chunk):
+        with torch.no_grad():
+            out = ol.render(H, W, K, chunk=chunk, c2w=pose.to(dev)[:3, :4], ndc=True, near=0., far=1., **test_kw)
+        assert tuple(out[0].shape) == (H, W, 3) and tuple(out[1].shape) == (H, W)
+        assert set(out[6]) == {"rgb0", "disp0", "acc0", "albedo0", "shading0", "residual0", "z_std"}
+        return out
+
+    out = frame(args.chunk)
+    names = ("rgb_fine", "disp_fine", "acc_fine", "albedo_fine", "shading_fine", "residual_fine")
+    got = {k: v.reshape(n, -1).squeeze(-1).cpu().numpy() for k, v in zip(names, out[:6])}
+    for rk, ok in (("rgb0", "rgb_coarse"), ("disp0", "disp_coarse"), ("acc0", "acc_coarse"), ("albedo0", "albedo_coarse"),
+                   ("shading0", "shading_coarse"), ("residual0", "residual_coarse"), ("z_std", "z_std")):
+        got[ok] = out[6][rk].reshape(n, -1).squeeze(-1).cpu().numpy()
+    assert set(got) == {k[4:] for k in fx if k.startswith("ref_")}
+    problems, summary = uncurated_judge(fx, got, f"render(ndc=True)/{precision}")
+    print("\n" + summary)
+    assert not problems, "\n".join(problems) + "\n" + summary
+    # chunk invariance on the NDC path: 128 does not divide the frame's 192 rays
+    flat = lambda o: list(o[:6]) + [o[6][k] for k in sorted(o[6])]
+    same = lambda a, b: all(torch.equal(torch.nan_to_num(x), torch.nan_to_num(y)) and torch.equal(torch.isnan(x), torch.isnan(y))
+                            for x, y in zip(flat(a), flat(b)))
+    assert n % 128 != 0
+    assert same(frame(128), out), "coalesced launch of 128-ray chunks differs from the one-chunk frame"
+    monkeypatch.setenv("INERF_COALESCE_BYTES", "0")
+    assert same(frame(128), out), "per-chunk launches (INERF_COALESCE_BYTES=0, chunk 128) differ from the one-chunk frame"
 
 
 def room_config(c=28):

@@ -128,7 +128,8 @@ def test_fine_stage_on_reference_depths(name):
 # ------------------------------------------------------------------------------------------------
 # the reference-signature front-ends
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["object_chair_det", "object_chair_train_rng", "object_coarse_only_lindisp"])
+@pytest.mark.parametrize("name", ["object_chair_det", "object_chair_train_rng", "object_coarse_only_lindisp", "object_llff_det",
+                                  "object_llff_train_gaussian"])
 def test_object_level_render_rays_frontend(name):
     from intrinsicnerf_amd import object_level as ol
     fx = load_golden(name)
@@ -411,6 +412,28 @@ def test_sample_coarse_bit_exact():
             want = oracle.coarse_depths(rays[:, 6:7], rays[:, 7:8], t, lindisp, t_rand)
             got = kernels.sample_coarse(rays.to(dev), t.to(dev), None if t_rand is None else t_rand.to(dev), lindisp)
             assert torch.equal(got.cpu(), want), f"lindisp={lindisp} perturb={t_rand is not None}"
+    # near = 0, as every NDC ray has (the LLFF configs: run_nerf.py:690-696): the first unperturbed depth is exactly 0.  With
+    # lindisp the reference divides by near: 1/0 = inf gives depth 0 where t < 1 and inf * 0 = NaN at t = 1 (and NaN spreads
+    # through the jittered neighbours) - the same non-finite values at the same places, the finite ones bit for bit
+    rays0 = rays.clone()
+    rays0[:, 6] = 0.0
+    rays0[:5, 7] = 1.0
+    for lindisp in (False, True):
+        for t_rand in (None, tr):
+            want = oracle.coarse_depths(rays0[:, 6:7], rays0[:, 7:8], t, lindisp, t_rand)
+            got = kernels.sample_coarse(rays0.to(dev), t.to(dev), None if t_rand is None else t_rand.to(dev), lindisp).cpu()
+            tag = f"near=0 lindisp={lindisp} perturb={t_rand is not None}"
+            if not lindisp:
+                assert torch.equal(got, want), tag
+                if t_rand is None:
+                    assert torch.equal(got[:, 0], torch.zeros(n)), tag
+                continue
+            assert not torch.isfinite(want).all(), tag          # the case is what it claims to be
+            assert torch.equal(torch.isnan(got), torch.isnan(want)), f"{tag}: NaN positions"
+            assert torch.equal(torch.isposinf(got), torch.isposinf(want)) and torch.equal(torch.isneginf(got), torch.isneginf(want)), \
+                f"{tag}: inf positions"
+            fin = torch.isfinite(want)
+            assert torch.equal(got[fin], want[fin]), f"{tag}: finite values"
 
 
 def test_f16_range_guard(precision):

@@ -100,6 +100,8 @@ def test_oracle_equals_the_live_reference_on_random_configurations():
     out = subprocess.run([sys.executable, script, "--cases", "6", "--seed", "1"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "oracle == reference on 18 random configurations" in out.stdout
+    # the draws of this seed include the LLFF configs' pieces: NDC rays, 64 importance samples, Gaussian raw noise
+    assert " ndc " in out.stdout and "+64 " in out.stdout and "noise=randn" in out.stdout, out.stdout
 
 
 @pytest.mark.parametrize("name", golden_names("uncurated_"))
