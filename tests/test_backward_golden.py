@@ -322,6 +322,20 @@ def test_network_backward_vs_torch_autograd(variant, c, endpoint, n, s, form, mo
     point counts: raw and every parameter gradient of kernels.mlp_train against torch autograd through the module's own
     forward on the same GPU.  The default training forward is the two-workgroup kernel; `single` forces the one-workgroup
     one, which SSR renders with the endpoint feature always use."""
+    _check_network_backward(variant, c, endpoint, n, s, form, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,c,endpoint,n,s", [("object", 0, False, 1024, 192), ("ssr", 28, False, 512, 192)])
+def test_network_backward_vs_fp64_autograd_at_the_training_batch(variant, c, endpoint, n, s, monkeypatch):
+    """The same at the fine batch a training step runs: 1024 rays x (64 + 128) samples of the object-level network, and the
+    reference's SSR step, 32 x 16 rays x (64 + 128) samples (three 64-point tiles per workgroup of the chain).  Default forms only:
+    raw and every parameter gradient of the whole one-call backward - chain, split-K weight-gradient products, reduction -
+    against fp64 autograd, with the ReLU ties masked, at 2e-4 of each tensor's norm."""
+    _check_network_backward(variant, c, endpoint, n, s, "default", monkeypatch)
+
+
+def _check_network_backward(variant, c, endpoint, n, s, form, monkeypatch):
     from intrinsicnerf_amd import kernels, object_level as ol, ssr
     if form == "single":
         if endpoint:

@@ -508,6 +508,30 @@ def test_abi_version_and_stale_library_guard(capi, monkeypatch, tmp_path):
     assert capi.lib().inerf_abi_version() == capi.ABI_VERSION
 
 
+def test_every_quoted_include_is_in_the_source_digest():
+    """Every #include "..." of csrc/*.{hip,cpp,h} - and of the headers those reach - names a file that source_digest() and the object
+    cache key read (_build.SOURCES / HEADERS): an edit to a header outside them would leave a stale libinerf.so looking current, and
+    the GPU suite would test the old binary (mlp_f16_pp.h, included by mlp_f16_t128.hip, was missing)."""
+    import glob
+    from intrinsicnerf_amd import _build
+    covered = {os.path.realpath(p) for p in _build._source_paths()}
+    assert {os.path.realpath(h) for h in _build.HEADERS} <= covered
+    todo = sorted(sum((glob.glob(os.path.join(_build.CSRC, "*." + ext)) for ext in ("hip", "cpp", "h")), []))
+    seen, missing = set(), []
+    while todo:
+        path = os.path.realpath(todo.pop())
+        if path in seen:
+            continue
+        seen.add(path)
+        for name in re.findall(r'^\s*#\s*include\s*"([^"]+)"', open(path).read(), flags=re.M):
+            inc = os.path.realpath(os.path.join(os.path.dirname(path), name))
+            assert os.path.exists(inc), f"{path}: #include \"{name}\" does not resolve"
+            if inc not in covered:
+                missing.append(f"{os.path.relpath(path, REPO)}: {name}")
+            todo.append(inc)
+    assert len(seen) > 10 and not missing, missing
+
+
 def test_workspace_skips_caller_provided_stage_tensors(capi):
     """inerf_render_workspace_bytes: stage tensors the caller supplies as outputs get no workspace region (raw was
     held twice - ~6 GB per chunk at C = 101 with the endpoint feature)."""

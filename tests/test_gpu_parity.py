@@ -321,8 +321,9 @@ def test_encode_mlp_raw(variant, c, s):
 def test_ssr_semantic_head_forms_agree(c, precision, monkeypatch):
     """The SSR network's two semantic-head forms of the two-workgroup kernel - per wave (every wave the whole head for its 16
     points) and channel-split (hidden layer split over the waves, partial logits through an L2-resident scratch; the default
-    for C <= 32, forced here for every C: more than 32 classes go block by block through the exchange area) - against the
-    oracle and against each other: the 11 base channels bit for bit, the logits up to their summation order."""
+    for C <= 32, forced here for every C: more than 32 classes go block by block through the exchange area) - and the opt-in
+    128-point tile (INERF_F16_KERNEL=t128, C <= 32) against the oracle and against each other: the 11 base channels bit for bit,
+    the logits up to their summation order."""
     from intrinsicnerf_amd import kernels
     if precision != "f16x3":
         pytest.skip("forms of the default f16x3 kernel")
@@ -337,7 +338,7 @@ def test_ssr_semantic_head_forms_agree(c, precision, monkeypatch):
     with torch.no_grad():
         want = oracle.query_network(sd, rays[:, None, 0:3] + rays[:, None, 3:6] * z[:, :, None], rays[:, 8:11], cfg)
     out = {}
-    for form in ("wave", "csplit", "t128"):     # t128: the 128-point tile (the default for C <= 32; more classes take the per-wave head)
+    for form in ("wave", "csplit", "t128"):     # t128: the 128-point tile (opt-in for SSR, C <= 32 only; more classes take the per-wave head)
         monkeypatch.setenv("INERF_F16_KERNEL", form)
         raw = kernels.encode_mlp(_desc(cfg), _packed(cfg, sd), rays.to(dev), z.to(dev))
         assert_maps_close(raw.cpu().numpy(), want.numpy(), RTOL, ATOL, f"raw C={c} {form}")
