@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40008
+#define INERF_ABI_VERSION 40009
 
 /* error codes */
 #define INERF_OK              0
@@ -429,6 +429,55 @@ int inerf_cluster_lookup(const float* rgb, const int64_t* label, int64_t n_pixel
                          const int32_t* links, const int32_t* anchor_begin, const float* factor, const float* centers,
                          const int32_t* center_begin, int n_classes, uint32_t flags, float* out_color,
                          int64_t* out_class, void* stream);
+
+/* Mean-shift fitting of the albedo clusters, every semantic class of a manager in one call: the tables that
+ * inerf_cluster_lookup reads.  Replaces Cluster_Manager.update_center (SSR/training/cluster.py:52-70) and, per class,
+ * Cluster.update_center (:138-152): mapping_color_np, sklearn's estimate_bandwidth(quantile, n_samples, random_state=0),
+ * max(bw * band_factor, 0.01), MeanShift(bandwidth, bin_seeding=True).fit, choose_anchors (:156-182) and
+ * inv_mapping_color (:335-341).
+ *   pixels[n,3] rgb; labels[n] int64 (NULL: every pixel belongs to class 0, the SSR class_num == 1 path; labels outside
+ *   [0, K) belong to no class).  Class c's pixels are taken in their original order.
+ *   sample_idx = the estimate_bandwidth subsample of every class, back to back: class c's indices (into the class's
+ *   pixels, in that order) are sample_idx[sample_begin[c] .. sample_begin[c+1]), i.e.
+ *   RandomState(0).permutation(n_c)[:n_samples] computed by the caller; max_class_samples = the largest such range
+ *   (at most 8192).  factor[K] = intensity_factor of each class.  All arrays are device pointers.
+ * Outputs (device): out_bandwidth[K] (0 for a class without pixels); out_center_begin[K+1] / out_centers[n,3] (rgb
+ *   centres, clamped to [0,1]); out_anchor_begin[K+1] / out_anchors[n,3] / out_links[n] (int64, centre index inside the
+ *   class) - every array sized for n rows, class c owning rows begin[c] .. begin[c+1].  Optional (may be NULL):
+ *   out_mapped_centers[n,3] (cluster_centers_ in the mapped space), out_center_counts[n] (points within bw of each
+ *   centre), out_pixel_label[n] (labels_ of every pixel in its class, -1 outside every class), out_class_stats[K,4]
+ *   (pixels, seeds, non-empty seeds, centres).  status[4] (device int32): status[0] bit 1 = a non-finite mapped colour,
+ *   bit 2 = a mapped colour of magnitude >= 256 (unsupported), bit 4 = a sample index outside its class; the outputs are
+ *   meaningless when it is not 0.  Limits: n < 2^24, K <= 255 (INERF_E_UNSUPPORTED beyond). */
+typedef struct inerf_cluster_fit_args {
+    const float* pixels;
+    const int64_t* labels;
+    int64_t n_pixels;
+    int32_t n_classes;
+    int32_t max_class_samples;
+    const int32_t* sample_idx;
+    const int32_t* sample_begin;
+    int64_t n_sample_idx;
+    const float* factor;
+    double quantile;
+    double band_factor;
+    void* workspace;
+    int64_t workspace_bytes;
+    double* out_bandwidth;
+    float* out_centers;
+    int32_t* out_center_begin;
+    float* out_anchors;
+    int64_t* out_links;
+    int32_t* out_anchor_begin;
+    float* out_mapped_centers;
+    int32_t* out_center_counts;
+    int32_t* out_pixel_label;
+    int32_t* out_class_stats;
+    int32_t* status;
+} inerf_cluster_fit_args;
+/* workspace of inerf_cluster_fit in bytes (negative INERF_E_* for bad sizes); n_sample_idx = total subsample indices */
+int64_t inerf_cluster_fit_workspace_bytes(int64_t n_pixels, int n_classes, int64_t n_sample_idx);
+int inerf_cluster_fit(const inerf_cluster_fit_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Networks outside the fused architecture, and fp32 training batches: one launch per nn.Linear on the fp32 matrix core.

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40008          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40009          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -53,6 +53,20 @@ class LinearArgs(C.Structure):
 
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
+
+
+class ClusterFitArgs(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("labels", C.c_void_p), ("n_pixels", C.c_int64), ("n_classes", C.c_int32),
+                ("max_class_samples", C.c_int32), ("sample_idx", C.c_void_p), ("sample_begin", C.c_void_p),
+                ("n_sample_idx", C.c_int64), ("factor", C.c_void_p), ("quantile", C.c_double), ("band_factor", C.c_double),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out_bandwidth", C.c_void_p),
+                ("out_centers", C.c_void_p), ("out_center_begin", C.c_void_p), ("out_anchors", C.c_void_p),
+                ("out_links", C.c_void_p), ("out_anchor_begin", C.c_void_p), ("out_mapped_centers", C.c_void_p),
+                ("out_center_counts", C.c_void_p), ("out_pixel_label", C.c_void_p), ("out_class_stats", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+CLUSTER_FIT_NONFINITE, CLUSTER_FIT_RANGE, CLUSTER_FIT_SAMPLE = 1, 2, 4
 
 # every symbol include/inerf.h declares: (restype, argtypes)
 _P, _I, _L, _U = C.c_void_p, C.c_int, C.c_int64, C.c_uint32
@@ -104,6 +118,8 @@ SYMBOLS = {
     "inerf_gen_rays": (_I, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _U, _P, _P]),
     "inerf_frame_to_u8": (_I, [_P, _L, _P, _P]),
     "inerf_cluster_lookup": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _P]),
+    "inerf_cluster_fit_workspace_bytes": (_L, [_L, _I, _L]),
+    "inerf_cluster_fit": (_I, [C.POINTER(ClusterFitArgs), _P]),
     "inerf_linear": (_I, [C.POINTER(LinearArgs), _P]),
     "inerf_linear_wgrad_workspace_bytes": (_L, [_L, _I, _I]),
     "inerf_linear_wgrad": (_I, [_P, _L, _I, _P, _L, _I, _L, _P, _P, _I, _P, _L, _P]),

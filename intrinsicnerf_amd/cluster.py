@@ -12,14 +12,23 @@ Two ways in:
   attributes (``class_num``, ``clusters[i].anchors / .links / .rgb_centers / .intensity_factor``), so the reference's own
   ``Cluster_Manager`` - including one that just ran its mean-shift ``update_center`` - can be handed over as it is;
 * ``Cluster`` / ``Cluster_Manager`` below read and write the reference's ``clusters.json`` / ``c<i>/config.json`` files
-  (cluster.py:20-50,112-129) and expose the same two lookups.  Building clusters (mean-shift on the CPU with sklearn,
-  cluster.py:138-182) is training control plane and stays with the reference.
+  (cluster.py:20-50,112-129) and expose the same two lookups.
+
+Building clusters - the reference's mean-shift ``update_center`` (cluster.py:52-70,138-182: sklearn's estimate_bandwidth,
+``MeanShift(bin_seeding=True)`` on one CPU thread, the voxel filter of the anchors) - is ``fit``: ONE call of
+``inerf_cluster_fit`` (csrc/cluster_fit.hip) for every class of a manager.  Only estimate_bandwidth's subsample
+(``RandomState(0).permutation``, numpy's legacy stream) is drawn on the host and handed over as indices.
+``update_center(manager, labels, pixels)`` fills any object with the reference's attributes (the reference's own
+``Cluster_Manager`` included); ``Cluster.update_center`` / ``Cluster_Manager.update_center`` below are the same call.
 
 There is no CPU path: pixels that are not on a HIP device raise.
 """
+import ctypes as C
 import json
 import os
+import sys
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -143,6 +152,180 @@ def dest_class(manager, rgb, label):
     return cls[:, None]
 
 
+MAX_CLASS_SAMPLES = 8192          # subsample rows the k-th neighbour kernel holds per class
+
+
+def sample_indices(counts, n_samples=5000, random_state=0):
+    """estimate_bandwidth's subsample of every class (sklearn/cluster/_mean_shift.py: ``check_random_state(0)`` and
+    ``permutation(n)[:n_samples]``): (int32 indices into each class's pixels in their original order, back to back;
+    int32 begin offsets [K+1])."""
+    parts, begin = [], [0]
+    for n_c in counts:
+        n_c = int(n_c)
+        if n_c <= 0:
+            idx = np.zeros(0, np.int64)
+        elif n_samples is None:
+            idx = np.arange(n_c)
+        else:
+            idx = np.random.RandomState(random_state).permutation(n_c)[:n_samples]
+        parts.append(idx.astype(np.int32))
+        begin.append(begin[-1] + idx.shape[0])
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int32)), np.asarray(begin, np.int32)
+
+
+class FitResult:
+    """What ``inerf_cluster_fit`` returns for the K classes of one manager.  Per class c (``None`` for a class without
+    pixels): ``centers[c]`` rgb [C,3] float32, ``anchors[c]`` [A,3] float32, ``links[c]`` [A,1] int64 - device tensors;
+    ``bandwidth[c]`` (float).  Intermediate results for tests: ``mapped_centers`` (sklearn's cluster_centers_),
+    ``center_counts``, ``pixel_label`` ([n] labels_ of every pixel inside its class, -1 outside), ``stats`` [K,4] (pixels,
+    seeds, non-empty seeds, centres)."""
+
+
+def _device_of(device):
+    device = torch.device("cuda") if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"cluster fitting runs on a HIP device, not {device} (no CPU fallback exists)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def fit(pixels, labels, class_num, factors, device=None, quantile=0.3, n_samples=5000, band_factor=0.5, sample=None):
+    """Mean-shift clusters of every class: ``labels`` None = every pixel in class 0 (the SSR ``class_num == 1`` path);
+    ``factors`` = intensity_factor per class; ``sample`` = (indices, begin) to override ``sample_indices``."""
+    device = _device_of(device)
+    K = int(class_num)
+    if isinstance(pixels, torch.Tensor):
+        px = pixels.detach().reshape(-1, 3).to(device=device, dtype=torch.float32).contiguous()
+    else:
+        px = torch.from_numpy(np.ascontiguousarray(np.asarray(pixels, dtype=np.float32).reshape(-1, 3))).to(device)
+    n = px.shape[0]
+    if labels is None:
+        lab_host, lab_dev = None, None
+        counts = np.array([n] + [0] * (K - 1), np.int64)
+    else:
+        lab_host = (labels.detach().reshape(-1).cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels).reshape(-1))
+        lab_host = lab_host.astype(np.int64)
+        if lab_host.shape[0] != n:
+            raise ValueError(f"{lab_host.shape[0]} labels for {n} pixels")
+        inside = lab_host[(lab_host >= 0) & (lab_host < K)]
+        counts = np.bincount(inside, minlength=K)[:K]
+        lab_dev = torch.from_numpy(lab_host).to(device)
+    res = FitResult()
+    res.counts = counts
+    idx, begin = sample_indices(counts, n_samples) if sample is None else sample
+    res.sample_idx, res.sample_begin = idx, begin
+    empty = [None] * K
+    if n == 0 or int(counts.sum()) == 0:
+        res.bandwidth, res.centers, res.anchors, res.links, res.mapped_centers, res.center_counts = [0.0] * K, empty, empty, empty, empty, empty
+        res.pixel_label = torch.full((n,), -1, dtype=torch.int32, device=device)
+        res.stats = np.zeros((K, 4), np.int64)
+        return res
+    max_s = int(np.diff(begin).max()) if K else 0
+    if max_s > MAX_CLASS_SAMPLES:
+        raise ValueError(f"n_samples={n_samples}: the bandwidth subsample of a class is at most {MAX_CLASS_SAMPLES} pixels here")
+    factor = torch.tensor([float(f) for f in factors], dtype=torch.float32, device=device)
+    idx_d = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(device)
+    begin_d = torch.from_numpy(np.ascontiguousarray(begin, dtype=np.int32)).to(device)
+    lib = _capi.lib()
+    ws_bytes = lib.inerf_cluster_fit_workspace_bytes(n, K, int(idx.shape[0]))
+    if ws_bytes < 0:
+        _capi.check(int(ws_bytes) if ws_bytes >= -4 else _capi.E_INVALID, "inerf_cluster_fit_workspace_bytes")
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=device)
+    f32 = dict(dtype=torch.float32, device=device)
+    centers, anchors, mapped = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
+    links = torch.empty(n, dtype=torch.int64, device=device)
+    center_counts = torch.empty(n, dtype=torch.int32, device=device)
+    pixel_label = torch.empty(n, dtype=torch.int32, device=device)
+    # bandwidth [K] doubles, then int32: status[4], center_begin[K+1], anchor_begin[K+1], stats[K,4] - read back at once
+    n_int = 4 + 2 * (K + 1) + 4 * K
+    meta = torch.zeros(K + (n_int + 1) // 2, dtype=torch.float64, device=device)
+    ints = meta[K:].view(torch.int32)
+    a = _capi.ClusterFitArgs(
+        pixels=px.data_ptr(), labels=None if lab_dev is None else lab_dev.data_ptr(), n_pixels=n, n_classes=K,
+        max_class_samples=max_s, sample_idx=idx_d.data_ptr(), sample_begin=begin_d.data_ptr(), n_sample_idx=int(idx.shape[0]),
+        factor=factor.data_ptr(), quantile=float(quantile), band_factor=float(band_factor), workspace=ws.data_ptr(),
+        workspace_bytes=int(ws_bytes), out_bandwidth=meta.data_ptr(), out_centers=centers.data_ptr(),
+        out_center_begin=ints[4:].data_ptr(), out_anchors=anchors.data_ptr(), out_links=links.data_ptr(),
+        out_anchor_begin=ints[4 + K + 1:].data_ptr(), out_mapped_centers=mapped.data_ptr(),
+        out_center_counts=center_counts.data_ptr(), out_pixel_label=pixel_label.data_ptr(),
+        out_class_stats=ints[4 + 2 * (K + 1):].data_ptr(), status=ints.data_ptr())
+    with torch.cuda.device(device):
+        rc = lib.inerf_cluster_fit(C.byref(a), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    _capi.check(rc, "inerf_cluster_fit")
+    host = meta.cpu()                                  # the one read: bandwidths, status, table offsets
+    hi = host[K:].view(torch.int32).numpy()
+    status = int(hi[0])
+    if status & _capi.CLUSTER_FIT_NONFINITE:
+        raise ValueError("cluster fit: a mapped colour is NaN or infinite (zero-intensity pixel?) - sklearn rejects such input too")
+    if status & _capi.CLUSTER_FIT_RANGE:
+        raise RuntimeError("cluster fit: a mapped colour has magnitude >= 256, outside what the kernels support")
+    if status & _capi.CLUSTER_FIT_SAMPLE:
+        raise ValueError("cluster fit: a subsample index lies outside its class")
+    cb, ab = hi[4:4 + K + 1], hi[4 + K + 1:4 + 2 * (K + 1)]
+    res.stats = hi[4 + 2 * (K + 1):4 + 2 * (K + 1) + 4 * K].reshape(K, 4).astype(np.int64)
+    res.bandwidth = [float(v) for v in host[:K].numpy()]
+    res.centers, res.anchors, res.links, res.mapped_centers, res.center_counts = [], [], [], [], []
+    for c in range(K):
+        if counts[c] == 0:
+            for lst in (res.centers, res.anchors, res.links, res.mapped_centers, res.center_counts):
+                lst.append(None)
+            continue
+        res.centers.append(centers[cb[c]:cb[c + 1]].clone())
+        res.mapped_centers.append(mapped[cb[c]:cb[c + 1]].clone())
+        res.center_counts.append(center_counts[cb[c]:cb[c + 1]].clone())
+        res.anchors.append(anchors[ab[c]:ab[c + 1]].clone())
+        res.links.append(links[ab[c]:ab[c + 1]].clone().reshape(-1, 1))
+    res.pixel_label = pixel_label
+    return res
+
+
+def _fill(cluster, res, c):
+    cluster.anchors, cluster.links, cluster.rgb_centers = res.anchors[c], res.links[c], res.centers[c]
+    return cluster
+
+
+def _cluster_factory(manager, device):
+    """Cluster objects of the manager's own kind: the class named ``Cluster`` in the manager's module (the reference's
+    for the reference's manager), this module's otherwise."""
+    cls = getattr(sys.modules.get(type(manager).__module__), "Cluster", None)
+    if cls is None or cls is Cluster:
+        return lambda: Cluster(device=device)
+    return cls
+
+
+def update_center(manager, labels, pixels, quantile=0.3, n_samples=5000, band_factor=0.5, cluster_factory=None):
+    """``Cluster_Manager.update_center`` (SSR/training/cluster.py:52-70) on the GPU for any object with the reference's
+    attributes: ``manager.clusters`` becomes one fitted cluster per class (``None`` for a class without pixels).  With
+    ``class_num == 1`` every pixel is fitted and the labels are ignored (:55-59)."""
+    K = int(manager.class_num)
+    device = _device_of(getattr(manager, "device", None))
+    make = cluster_factory or _cluster_factory(manager, device)
+    first = make()
+    factor = float(getattr(first, "intensity_factor", 0.5))          # Cluster() defaults: the reference fits with 0.5
+    res = fit(pixels, None if K == 1 else labels, K, [factor] * K, device=getattr(first, "device", device), quantile=quantile,
+              n_samples=n_samples, band_factor=band_factor)
+    clusters = []
+    for c in range(K):
+        if res.centers[c] is None:
+            clusters.append(None)
+        else:
+            clusters.append(_fill(first, res, c))
+            first = make()
+    manager.clusters = clusters
+    return res
+
+
+def fit_cluster(cluster, pixels, quantile=0.3, n_samples=5000, band_factor=0.5):
+    """``Cluster.update_center`` (cluster.py:138-152) on the GPU: fills ``cluster.anchors / links / rgb_centers``."""
+    res = fit(pixels, None, 1, [float(cluster.intensity_factor)], device=getattr(cluster, "device", None), quantile=quantile,
+              n_samples=n_samples, band_factor=band_factor)
+    if res.centers[0] is None:
+        raise ValueError("cluster fit: no pixels")
+    _fill(cluster, res, 0)
+    return res
+
+
 class Cluster:
     """Data holder with the reference's ``Cluster`` fields and file format (cluster.py:101-129)."""
 
@@ -180,9 +363,12 @@ class Cluster:
     def dest_class(self, rgb):
         return lookup(tables_for(self, [self], rgb.device), rgb, want_color=False, want_class=True, ignore_label=True)[1][:, None]
 
+    def update_center(self, pixels, quantile=0.3, n_samples=5000, band_factor=0.5):
+        fit_cluster(self, pixels, quantile=quantile, n_samples=n_samples, band_factor=band_factor)
+
 
 class Cluster_Manager:
-    """The reference's ``Cluster_Manager`` minus the mean-shift fitting (cluster.py:12-98)."""
+    """The reference's ``Cluster_Manager`` (cluster.py:12-98); ``update_center`` fits on the GPU (``fit``)."""
 
     def __init__(self, class_num=0, cluster_config_file=None, device=None):
         self.class_num = class_num
@@ -212,6 +398,9 @@ class Cluster_Manager:
             dirs.append(d)
         with open(os.path.join(cluster_manager_dir, "clusters.json"), "w") as f:
             json.dump({"class_num": self.class_num, "cluster_dirs": dirs}, f)
+
+    def update_center(self, labels, pixels, quantile=0.3, n_samples=5000, band_factor=0.5):
+        update_center(self, labels, pixels, quantile=quantile, n_samples=n_samples, band_factor=band_factor)
 
     def dest_color(self, rgb, label):
         return dest_color(self, rgb, label)

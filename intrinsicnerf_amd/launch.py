@@ -18,6 +18,11 @@ reference's own code looks them up in - and then executes the script's own main 
       SSRTrainer.render_rays / volumetric_rendering / create_ssr <- ssr.SSRRenderMixin's; run_network, raw2outputs,
       sample_pdf, create_rays, Semantic_NeRF, get_embedder in every SSR module that holds them; the two cluster lookups.
 
+``--inerf-cluster-fit`` (opt-in) also moves the mean-shift fit of the albedo clusters onto the GPU: the reference's
+``Cluster.update_center`` / ``Cluster_Manager.update_center`` become ``cluster.fit_cluster`` / ``cluster.update_center``
+(csrc/cluster_fit.hip), and with ``--inerf-render-path`` the mirrors' ``render_path`` builds the package's
+``Cluster_Manager``.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -57,21 +62,42 @@ def _kind(script):
     raise SystemExit(f"intrinsicnerf_amd.launch: {name}: expected the reference's object_level/run_nerf.py or train_SSR_main.py")
 
 
-def rebind_object_level(namespace, with_render_path=False):
+def rebind_cluster_fit(module_name):
+    """The GPU mean-shift fit onto the reference's ``Cluster`` / ``Cluster_Manager`` of ``module_name`` (if imported):
+    returns {qualified class name: [methods bound]}."""
+    from . import cluster as inerf_cluster
+    mod = sys.modules.get(module_name)
+    bound = {}
+    if mod is None:
+        return bound
+    if hasattr(mod, "Cluster"):
+        mod.Cluster.update_center = inerf_cluster.fit_cluster
+        bound[module_name + ".Cluster"] = ["update_center"]
+    if hasattr(mod, "Cluster_Manager"):
+        mod.Cluster_Manager.update_center = inerf_cluster.update_center
+        bound[module_name + ".Cluster_Manager"] = ["update_center"]
+    return bound
+
+
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
     names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ())
     for name in names:
         namespace[name] = getattr(object_level, name)
+    if cluster_fit:
+        rebind_cluster_fit("cluster")                  # run_nerf.py:24 `from cluster import Cluster, Cluster_Manager`
     if with_render_path and "Cluster_Manager" in namespace:
-        # run_nerf.py:818,1071 call render_path(update_cluster=True): the mean-shift fitting stays the reference's own class
-        # (run_nerf.py:24, :218), handed to the mirror as its factory
+        # run_nerf.py:818,1071 call render_path(update_cluster=True): the reference's own class (run_nerf.py:24, :218) is
+        # handed to the mirror as its factory - the package's GPU-fitted one under --inerf-cluster-fit
         import functools
-        namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=namespace["Cluster_Manager"])
+        from . import cluster as inerf_cluster
+        factory = inerf_cluster.Cluster_Manager if cluster_fit else namespace["Cluster_Manager"]
+        namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=factory)
     return names
 
 
-def rebind_ssr(with_render_path=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     bound = {}
@@ -83,7 +109,8 @@ def rebind_ssr(with_render_path=False):
         setattr(trainer.SSRTrainer, extra, getattr(ssr.SSRRenderMixin, extra))
     if with_render_path and hasattr(trainer, "Cluster_Manager"):
         # trainer.py:1065 renders with update_cluster = not self.no_cluster: the fitting is the reference's class (trainer.py:16, :1416-1418)
-        trainer.SSRTrainer.cluster_manager_factory = staticmethod(trainer.Cluster_Manager)
+        factory = inerf_cluster.Cluster_Manager if cluster_fit else trainer.Cluster_Manager
+        trainer.SSRTrainer.cluster_manager_factory = staticmethod(factory)
     bound["SSR.training.trainer.SSRTrainer"] = list(methods)
     for mod_name in SSR_MODULES:
         mod = sys.modules.get(mod_name)
@@ -98,10 +125,13 @@ def rebind_ssr(with_render_path=False):
         cl.Cluster_Manager.dest_color = inerf_cluster.dest_color
         cl.Cluster_Manager.dest_class = inerf_cluster.dest_class
         bound["SSR.training.cluster.Cluster_Manager"] = ["dest_color", "dest_class"]
+    if cluster_fit:
+        for name, methods in rebind_cluster_fit("SSR.training.cluster").items():
+            bound.setdefault(name, []).extend(methods)
     return bound
 
 
-def prepare(script, with_render_path=False):
+def prepare(script, with_render_path=False, cluster_fit=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -115,10 +145,10 @@ def prepare(script, with_render_path=False):
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit)
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit)
     return mod, main
 
 
@@ -127,13 +157,16 @@ def main(argv=None):
     with_render_path = "--inerf-render-path" in argv
     if with_render_path:
         argv.remove("--inerf-render-path")
+    cluster_fit = "--inerf-cluster-fit" in argv
+    if cluster_fit:
+        argv.remove("--inerf-cluster-fit")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
     script = argv[0]
     from . import _capi
     _capi.lib()                                        # fail now, and loudly, if the HIP library is missing
-    mod, main_code = prepare(script, with_render_path)
+    mod, main_code = prepare(script, with_render_path, cluster_fit)
     sys.argv = [script] + argv[1:]                     # the script's own argument parser sees its own command line
     mod.__dict__["__name__"] = "__main__"
     exec(main_code, mod.__dict__)
