@@ -190,6 +190,22 @@ __device__ __forceinline__ void split_store4(_Float16* hi_ptr, _Float16* lo_ptr,
     *reinterpret_cast<f16x4*>(lo_ptr) = lo4;
 }
 
+// A point's normaliser from its largest head gradient m: the power of two above m, its exponent kept within [-126, 126] so that s AND
+// 1 / s are finite normal numbers for every m > 0.  (Unclamped, a denormal m below 2^-128 - the transmittance behind an opaque
+// surface passes through that window - gave 1 / s = inf and inf - inf = NaN in every weight gradient of the step; m >= 2^127 gave
+// s = inf.)  At the clamp the normalised gradients are at most 4 instead of 1, or smaller than 1/2: both far inside f16's range.
+// 1 for a point without gradient, and for a non-finite one (which the range guard then reports).
+__device__ __forceinline__ float point_normaliser(float m) {
+    float s = 1.0f;
+    if (m > 0.0f && m < 3.0e38f) {
+        int e;
+        frexpf(m, &e);
+        e = e < -126 ? -126 : (e > 126 ? 126 : e);
+        s = ldexpf(1.0f, e);
+    }
+    return s;
+}
+
 // Pre-activation gradients of one point's output heads (albedo 3, shading 1, residual 3, sigma 1) from d loss / d raw and raw,
 // and the point's normaliser: the power of two above its largest head gradient (1 for a point without gradient).
 __device__ __forceinline__ float head_gradients(const BwdParams& p, int gp, bool sem, float (&dp)[8]) {
@@ -212,9 +228,7 @@ __device__ __forceinline__ float head_gradients(const BwdParams& p, int gp, bool
     for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(dp[k]));
     if (sem) for (int j = 0; j < p.n_classes; ++j) m = fmaxf(m, fabsf(g[INERF_BASE_CHANNELS + j]));
     if (p.endpoint) for (int c = 0; c < INERF_ENDPOINT_DIM; ++c) m = fmaxf(m, fabsf(g[ch - INERF_ENDPOINT_DIM + c]));
-    float s = 1.0f;
-    if (m > 0.0f && m < 3.0e38f) { int e; frexpf(m, &e); s = ldexpf(1.0f, e); }
-    return s;
+    return point_normaliser(m);
 }
 
 // The same in two halves (load, compute), for the two-workgroup chain.
@@ -244,9 +258,7 @@ __device__ __forceinline__ float head_gradients(const BwdParams& p, int gp, bool
     const float* __restrict__ g = p.d_raw + (size_t)gp * ch;
     if (sem) for (int j = 0; j < p.n_classes; ++j) m = fmaxf(m, fabsf(g[INERF_BASE_CHANNELS + j]));
     if (p.endpoint) for (int c = 0; c < INERF_ENDPOINT_DIM; ++c) m = fmaxf(m, fabsf(g[ch - INERF_ENDPOINT_DIM + c]));
-    float s = 1.0f;
-    if (m > 0.0f && m < 3.0e38f) { int e; frexpf(m, &e); s = ldexpf(1.0f, e); }
-    return s;
+    return point_normaliser(m);
 }
 
 // NW waves per workgroup: 4 (each wave 64 channels = RB 2 row blocks; one wave per SIMD) or 8 (32 channels each; TWO waves per

@@ -64,6 +64,18 @@ __device__ __forceinline__ void split8(const float (&v)[8], float scale, f16x8& 
     }
 }
 
+// 2^k that brings an operand bound m into [2^13, 2^14) (the f16 hi / lo pair's range), k kept at or below 126: the scale and its
+// reciprocal are finite normal numbers for every m (a batch whose largest gradient is below 2^-112 used to get the scale inf).  At
+// the clamp the operands sit lower in their pair - the lo half's 2^-24 steps still resolve 2^-31 of a bound of 2^-119 x 2^126.
+// The products are scaled back by 1 / sg and 1 / sx one after the other: their product alone may leave fp32's range.
+__device__ __forceinline__ float operand_pow2(float m) {
+    if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f;
+    int e;
+    frexpf(m, &e);
+    const int k = 14 - e;                      // >= -114: m is finite
+    return ldexpf(1.0f, k > 126 ? 126 : k);
+}
+
 // [32 points x 32 channels] block (two 16-channel pieces g0, g1, already split) -> operands with lane = channel:
 // out[q] holds, for k-block q of this 32-point half, 8 points of the lane's channel
 // returns the sum of the lane's 16 transposed values (= this lane's channel over 16 of the block's 32 points)
@@ -104,9 +116,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_mlp_wgrad(const WgradParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 31, lh = lane >> 5;
     // powers of two that bring the operands' bounds into [2^13, 2^14) (f16 hi/lo split range)
-    auto pow2_for = [](float m) { int e; if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f; frexpf(m, &e); return ldexpf(1.0f, 14 - e); };
     auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float sg = uniform(pow2_for(p.ranges[0])), sx = XFRAG ? kActScale : uniform(pow2_for(p.ranges[1]));       // wave-uniform: scalar registers
+    const float sg = uniform(operand_pow2(p.ranges[0])), sx = XFRAG ? kActScale : uniform(operand_pow2(p.ranges[1]));       // wave-uniform: scalar registers
 
     // identity operands of the transposer: B[k][n] = (n == k) resp. (n == k + 16); lane n holds k = 8 * lh + i
     f16x8 id0, id1;
@@ -293,7 +304,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_mlp_wgrad(const WgradParams p) {
     }
 
     // ---- this workgroup's partial tile: row m = channel of G, column n = channel of X ----
-    const float back = 1.0f / (sg * sx);
+    const float back_x = 1.0f / sx, back_g = 1.0f / sg;          // powers of two: exact, in either order, wherever the result is normal
     float* out = p.partial + (size_t)blockIdx.x * p.partial_stride;
 #ifdef INERF_WGRAD_STAMPS
     if (blockIdx.x == 0) {
@@ -314,7 +325,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_mlp_wgrad(const WgradParams p) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int m = 32 * wave + (j & 3) + 8 * (j >> 2) + 4 * lh;
-            out[(size_t)m * p.N + 32 * cb + lp] = acc[cb][j] * back;
+            out[(size_t)m * p.N + 32 * cb + lp] = acc[cb][j] * back_x * back_g;
         }
 }
 
@@ -441,8 +452,7 @@ __device__ __forceinline__ void wgrad_frag_body(const WgradFragParams& p, char* 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[cb][r] = 0.0f;
     float bias_sum = 0.0f;                     // this lane's channel of the wave's row block, its k-half's points (units of 1 / sg)
-    auto pow2_for = [](float m) { int e; if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f; frexpf(m, &e); return ldexpf(1.0f, 14 - e); };
-    const float sg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pow2_for(p.ranges[0]))));
+    const float sg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, operand_pow2(p.ranges[0]))));
     const float sgc = sg * (1.0f / kActScale);
     auto contract = [&](int buf) {
         const char* gset = ldsw + buf * kFragStageBytes + lane * 16;
@@ -503,14 +513,14 @@ __device__ __forceinline__ void wgrad_frag_body(const WgradFragParams& p, char* 
         if (lh == 0) bias_partial[(size_t)b * p.partial_stride + 32 * rbk + lp] = both / sg;
     }
     if (!contracts) return;
-    const float back = 1.0f / (sg * kActScale);
+    const float back_g = 1.0f / sg;
     float* out = p.partial[job] + (size_t)b * p.partial_stride;
 #pragma unroll
     for (int cb = 0; cb < NC; ++cb)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int m = 32 * rbk + (j & 3) + 8 * (j >> 2) + 4 * lh;
-            out[(size_t)m * (32 * XB) + 32 * (cb0 + cb) + lp] = acc[cb][j] * back;
+            out[(size_t)m * (32 * XB) + 32 * (cb0 + cb) + lp] = acc[cb][j] * (1.0f / kActScale) * back_g;
         }
 }
 
