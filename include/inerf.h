@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40009
+#define INERF_ABI_VERSION 40010
 
 /* error codes */
 #define INERF_OK              0
@@ -533,6 +533,86 @@ int inerf_embed(const float* rays, const float* z_vals, int64_t n_rays, int n_sa
  * residual given d_raw (the gradient of all raw channels) and raw (the forward's values); dz is [n_points, 8], dz[p, 7] = 0. */
 int inerf_intrinsic_combine(float* raw, int64_t ld, int64_t n_points, void* stream);
 int inerf_intrinsic_combine_backward(const float* raw, const float* d_raw, int64_t ld, int64_t n_points, float* dz, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The training losses of both trainers: every term of a step in ONE forward launch, every gradient in ONE backward launch.
+ *
+ * Replaces compute_intrinsic_loss (object_level/run_nerf_helpers.py:59-86, SSR/training/training_utils.py:179-207) with the
+ * helpers under it (compute_chroma_loss, compute_residual_loss, compute_chroma_weight, compute_reflect_sparsity_loss,
+ * compute_shading_smooth_loss, compute_intensity_loss: run_nerf_helpers.py:15-57, training_utils.py:127-176), img2mse
+ * (run_nerf_helpers.py:11, training_utils.py:124) on the image (run_nerf.py:976,1006; trainer.py:923,936) and on the cluster
+ * target (run_nerf.py:987,1012; trainer.py:985-986), nn.CrossEntropyLoss(ignore_index=-1) on label-1 (trainer.py:858-865,
+ * 927,939), and what loss.backward() records for all of them (run_nerf.py:1018, trainer.py:990).  compute_depth_weight is
+ * evaluated by the reference and then replaced by the literal 1 (run_nerf_helpers.py:78-84): disp and acc are not inputs.
+ *
+ * n_levels = 1 (one compute_intrinsic_loss call) or 2 (coarse = level 0 and fine = level 1 of one step); the levels share
+ * gt_rgb, pair_key, cluster_target and ce_labels.  Pairing: split = n/2, ray i < split pairs with ray i + (n - split) (an odd n
+ * leaves the middle ray unpaired); split2 = split/2, ray i < split2 pairs with ray i + (split - split2) (the "far" term).
+ *   pair_key: float mask[n] (target_m, run_nerf.py:703), or with INERF_LOSS_KEY_LABELS int64 labels[n] compared as integers
+ *     (training_utils.py:148) - the shading weight is then unmasked (training_utils.py:150).
+ *   INERF_LOSS_MASK_OUTER: the mask was [n,1]; the reference's broadcast then forms a [split,split] matrix whose mean is
+ *     mean(mask product) * mean(weight * distance) for the sparsity, shading and far terms: that factorised form is computed.
+ *   level[l].rgb (optional, both levels or none): adds img2mse(rgb, gt_rgb).  cluster_target[n,3] (optional): adds
+ *     img2mse(albedo, cluster_target).  level[l].logits[n, n_classes] + ce_labels[n] int64 (optional, both or none; n_classes
+ *     in 1..INERF_LOSS_MAX_CLASSES): adds the cross-entropy; ce_label_offset is added to every label first (-1 = the
+ *     reference's label-1 taken from the unshifted labels, 0 = already shifted); a label outside [0, n_classes) afterwards
+ *     is ignored, the mean is taken over the others (none left: NaN, as torch).
+ * state (device, inerf_intrinsic_loss_workspace_bytes): written by the forward, read by the backward -
+ *   state[l*16 + t], t = INERF_LOSS_TERM_*: the terms of level l (absent ones 0), then [9] rgb_mean - albedo_mean, [10] / [11]
+ *   mean mask product of the near / far pairs, [12] number of rays the cross-entropy counted;
+ *   state[n_levels*16] = the weighted total sum_l sum_t weights[t] * term[l][t] over the terms that are present.
+ * weights[INERF_LOSS_TERMS] (device; NULL = all 1).  An empty mean is NaN as in torch (n < 4: the far term; n < 2: the pair terms).
+ * Backward: d(sum_l sum_t (grad_total[0] * weights[t] + grad_terms[l*INERF_LOSS_STATE_FLOATS + t]) * term[l][t]) with respect to every
+ *   differentiable input (grad_total, grad_terms: device, either may be NULL); d_albedo[n,3], d_shading[n], d_residual[n,3] are
+ *   required, d_rgb[n,3] / d_logits[n,n_classes] where the forward had rgb / logits.  One thread per ray gathers its own
+ *   contributions (no atomics); both launches are bit-identical from run to run and read nothing on the host. */
+#define INERF_LOSS_KEY_LABELS   1u
+#define INERF_LOSS_MASK_OUTER   2u
+#define INERF_LOSS_TERMS        9
+#define INERF_LOSS_TERM_CHROMA    0
+#define INERF_LOSS_TERM_RESIDUAL  1
+#define INERF_LOSS_TERM_SPARSITY  2
+#define INERF_LOSS_TERM_SHADING   3
+#define INERF_LOSS_TERM_FAR       4
+#define INERF_LOSS_TERM_INTENSITY 5
+#define INERF_LOSS_TERM_IMAGE     6
+#define INERF_LOSS_TERM_CLUSTER   7
+#define INERF_LOSS_TERM_SEMANTIC  8
+#define INERF_LOSS_STATE_FLOATS   16   /* per level */
+#define INERF_LOSS_MAX_CLASSES    101
+typedef struct inerf_loss_level {
+    const float* albedo;
+    const float* shading;
+    const float* residual;
+    const float* rgb;
+    const float* logits;
+    float* d_albedo;
+    float* d_shading;
+    float* d_residual;
+    float* d_rgb;
+    float* d_logits;
+} inerf_loss_level;
+typedef struct inerf_loss_args {
+    int64_t n_rays;
+    int32_t n_levels;
+    int32_t n_classes;
+    uint32_t flags;
+    int32_t ce_label_offset;
+    const float* gt_rgb;
+    const void* pair_key;
+    const float* cluster_target;
+    const int64_t* ce_labels;
+    const float* weights;
+    const float* grad_total;
+    const float* grad_terms;
+    inerf_loss_level level[2];
+    float* state;
+    int64_t state_bytes;
+} inerf_loss_args;
+/* bytes of `state` (negative INERF_E_* for bad sizes) */
+int64_t inerf_intrinsic_loss_workspace_bytes(int64_t n_rays, int n_levels);
+int inerf_intrinsic_loss(const inerf_loss_args* args, void* stream);
+int inerf_intrinsic_loss_backward(const inerf_loss_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
 
   object_level   drop-in for object_level/run_nerf.py + run_nerf_helpers.py (render, render_rays, ...)
   ssr            drop-in for SSR/ + train_SSR_main.py's render path (SSRRenderMixin, Semantic_NeRF, ...)
+  losses         the trainers' loss terms, one forward and one backward launch (compute_intrinsic_loss, *_step_loss)
   kernels        tensor-level launchers of the C ABI (include/inerf.h, libinerf.so)
   packing        state dict -> MFMA-fragment-ordered weight blob
   distributed    ray sharding across the GPUs of a node + RCCL gather of the rendered maps

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40009          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40010          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -65,6 +65,22 @@ class ClusterFitArgs(C.Structure):
                 ("out_center_counts", C.c_void_p), ("out_pixel_label", C.c_void_p), ("out_class_stats", C.c_void_p),
                 ("status", C.c_void_p)]
 
+
+class LossLevel(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("albedo", "shading", "residual", "rgb", "logits",
+                                          "d_albedo", "d_shading", "d_residual", "d_rgb", "d_logits")]
+
+
+class LossArgs(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_levels", C.c_int32), ("n_classes", C.c_int32), ("flags", C.c_uint32),
+                ("ce_label_offset", C.c_int32), ("gt_rgb", C.c_void_p), ("pair_key", C.c_void_p), ("cluster_target", C.c_void_p),
+                ("ce_labels", C.c_void_p), ("weights", C.c_void_p), ("grad_total", C.c_void_p), ("grad_terms", C.c_void_p),
+                ("level", LossLevel * 2), ("state", C.c_void_p), ("state_bytes", C.c_int64)]
+
+
+LOSS_KEY_LABELS, LOSS_MASK_OUTER = 1, 2
+LOSS_TERMS, LOSS_STATE_FLOATS, LOSS_MAX_CLASSES = 9, 16, 101
+LOSS_TERM_NAMES = ("chroma", "residual", "sparsity", "shading", "far", "intensity", "image", "cluster", "semantic")
 
 CLUSTER_FIT_NONFINITE, CLUSTER_FIT_RANGE, CLUSTER_FIT_SAMPLE = 1, 2, 4
 
@@ -126,6 +142,9 @@ SYMBOLS = {
     "inerf_embed": (_I, [_P, _P, _L, _I, _I, C.c_float, _I, _P, _L, _P]),
     "inerf_intrinsic_combine": (_I, [_P, _L, _L, _P]),
     "inerf_intrinsic_combine_backward": (_I, [_P, _P, _L, _L, _P, _P]),
+    "inerf_intrinsic_loss_workspace_bytes": (_L, [_L, _I]),
+    "inerf_intrinsic_loss": (_I, [C.POINTER(LossArgs), _P]),
+    "inerf_intrinsic_loss_backward": (_I, [C.POINTER(LossArgs), _P]),
 }
 
 _lib = None

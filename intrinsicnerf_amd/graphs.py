@@ -17,6 +17,10 @@ f16's range never reaches the optimizer: it is re-run eagerly (where the front-e
 layers) from the same RNG state.  Random draws inside the step (jitter, noise) use torch's graph-safe generator and advance
 on every replay.
 
+The ~115 small torch kernels above belong to a plain image loss; the reference's own loss (compute_intrinsic_loss on both levels,
+cluster MSE, cross-entropy) is ~300 more as torch expressions.  ``losses.object_step_loss`` / ``losses.ssr_step_loss`` are that loss
+as two captured launches - what a ``loss_fn`` here should end with.
+
 Learning-rate schedules: both reference trainers write ``param_group['lr'] = new_lrate`` every iteration (run_nerf.py:1024-1027,
 trainer.py:1006-1009).  A Python float would be baked into graph B's kernels at capture time, so every group's rate lives in a
 DEVICE tensor that the captured Adam reads; ``__call__`` notices a rate the trainer wrote into the group (any float, or another

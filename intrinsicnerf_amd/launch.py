@@ -23,6 +23,12 @@ reference's own code looks them up in - and then executes the script's own main 
 (csrc/cluster_fit.hip), and with ``--inerf-render-path`` the mirrors' ``render_path`` builds the package's
 ``Cluster_Manager``.
 
+``--inerf-losses`` (opt-in) moves the intrinsic loss terms onto the GPU kernels of csrc/losses.hip: ``compute_intrinsic_loss``
+becomes ``losses.compute_intrinsic_loss`` where the trainers look it up - ``run_nerf.py``'s own namespace
+(``from run_nerf_helpers import *``, called at run_nerf.py:977,1007) and ``SSR.training.trainer`` (imported by name at
+trainer.py:15, called at :924,937).  Six scalars in the reference's order through one autograd node; the trainers' weighted
+sums and ``loss.backward()`` stay their own lines.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -79,10 +85,13 @@ def rebind_cluster_fit(module_name):
     return bound
 
 
-def rebind_object_level(namespace, with_render_path=False, cluster_fit=False):
+LOSS_SYMBOL = "compute_intrinsic_loss"
+
+
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
-    names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ())
+    names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ()) + ((LOSS_SYMBOL,) if losses else ())
     for name in names:
         namespace[name] = getattr(object_level, name)
     if cluster_fit:
@@ -97,7 +106,7 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False):
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     bound = {}
@@ -128,10 +137,13 @@ def rebind_ssr(with_render_path=False, cluster_fit=False):
     if cluster_fit:
         for name, methods in rebind_cluster_fit("SSR.training.cluster").items():
             bound.setdefault(name, []).extend(methods)
+    if losses:                                         # trainer.py:15 holds the function by value; step() looks it up in its module
+        setattr(trainer, LOSS_SYMBOL, getattr(ssr, LOSS_SYMBOL))
+        bound.setdefault("SSR.training.trainer", []).append(LOSS_SYMBOL)
     return bound
 
 
-def prepare(script, with_render_path=False, cluster_fit=False):
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -145,10 +157,10 @@ def prepare(script, with_render_path=False, cluster_fit=False):
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses)
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses)
     return mod, main
 
 
@@ -160,13 +172,17 @@ def main(argv=None):
     cluster_fit = "--inerf-cluster-fit" in argv
     if cluster_fit:
         argv.remove("--inerf-cluster-fit")
+    losses = "--inerf-losses" in argv
+    if losses:
+        argv.remove("--inerf-losses")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
     script = argv[0]
     from . import _capi
     _capi.lib()                                        # fail now, and loudly, if the HIP library is missing
-    mod, main_code = prepare(script, with_render_path, cluster_fit)
+    # (positional as before for the first two; the loss flag only when given, so a two-flag `prepare` stand-in keeps working)
+    mod, main_code = prepare(script, with_render_path, cluster_fit, losses) if losses else prepare(script, with_render_path, cluster_fit)
     sys.argv = [script] + argv[1:]                     # the script's own argument parser sees its own command line
     mod.__dict__["__name__"] = "__main__"
     exec(main_code, mod.__dict__)

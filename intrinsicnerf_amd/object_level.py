@@ -18,9 +18,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _capi, kernels, layered, packing
+from .losses import compute_intrinsic_loss, object_step_loss  # noqa: F401  (run_nerf_helpers.py:59-86, run_nerf.py:976-1013 on csrc/losses.hip)
 
 __all__ = ["Embedder", "get_embedder", "NeRF", "NetworkQuery", "run_network", "raw2outputs", "sample_pdf",
-           "render_rays", "batchify_rays", "render", "render_path", "get_rays", "get_rays_np", "ndc_rays", "create_nerf", "to8b"]
+           "render_rays", "batchify_rays", "render", "render_path", "get_rays", "get_rays_np", "ndc_rays", "create_nerf", "to8b",
+           "compute_intrinsic_loss", "object_step_loss"]
 
 
 # ----------------------------------------------------------------------------------------------

@@ -18,9 +18,11 @@ import torch.nn.functional as F
 from . import _capi, kernels, layered, packing
 from .object_level import (FP32_LAYERS_NOTE, Embedder, _layered_spec, _run_network_torch, _train_desc, _train_query, _training_path_notice,
                            _wants_grad)
+from .losses import compute_intrinsic_loss_ssr as compute_intrinsic_loss, ssr_step_loss  # noqa: F401  (training_utils.py:179-207, trainer.py:923-988)
 
 __all__ = ["get_embedder", "Semantic_NeRF", "run_network", "raw2outputs", "sample_pdf", "create_rays",
-           "get_rays_camera", "get_rays_world", "batchify_rays", "SSRRenderMixin", "SSRRenderer"]
+           "get_rays_camera", "get_rays_world", "batchify_rays", "SSRRenderMixin", "SSRRenderer",
+           "compute_intrinsic_loss", "ssr_step_loss"]
 
 
 def get_embedder(multires, i=0, scalar_factor=1):

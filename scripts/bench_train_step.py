@@ -2,7 +2,10 @@
 """Training-step timing through the object-level front-end (staged path: HIP sampling / compositing with HIP backward,
 network layers through torch autograd) and the compositing kernels' HBM rates.
 
-    python scripts/bench_train_step.py [--rays 2048] [--iters 10]
+    python scripts/bench_train_step.py [--rays 2048] [--iters 10] [--ssr C] [--loss intrinsic]
+``--loss intrinsic`` times the step with the loss the reference trains with (compute_intrinsic_loss on both levels, image and
+cluster MSE, the SSR cross-entropy) instead of the default stand-in loss - once as torch expressions (scripts/torch_losses.py)
+and once on the two launches of csrc/losses.hip, alternating in the same process.
 The batch is the reference's: N_rand = 1024 rays plus one neighbour each (run_nerf.py:918-929), 64 + 128 samples.
 """
 import argparse
@@ -23,7 +26,29 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rays", type=int, default=2048)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--ssr", type=int, default=-1, help="C >= 0: the SSR network with C classes through ssr.SSRRenderer instead")
+ap.add_argument("--loss", choices=("mse", "intrinsic"), default="mse", help="intrinsic: the reference's full loss, as torch expressions and in HIP")
 a = ap.parse_args()
+LOSS_WEIGHTS = {"image": 1.0, "chroma": 1.0, "sparsity": 0.01, "far": 0.01, "shading": 1.0, "residual": 1.0, "intensity": 0.1, "cluster": 1.0,
+                "semantic": 0.04}
+
+
+def time_both(steps, iters, what):
+    """``steps``: {name: step function}; warms every one up, then times them in alternating rounds and prints the medians."""
+    import statistics
+    for fn in steps.values():
+        for _ in range(10):
+            fn()
+    times = {k: [] for k in steps}
+    for _ in range(5):
+        for k, fn in steps.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize(); times[k].append((time.perf_counter() - t0) / iters * 1e3)
+    for k, v in times.items():
+        print(f"{what}, intrinsic loss as {k}: {statistics.median(v):.2f} ms per step (rounds: {', '.join(f'{x:.2f}' for x in v)})")
+
+
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 if a.ssr >= 0:          # trainer.py:876-991: 1024 rays (512 + neighbours), depth range [0.1, 10], semantic cross-entropy + photometric loss
@@ -46,6 +71,29 @@ if a.ssr >= 0:          # trainer.py:876-991: 1024 rays (512 + neighbours), dept
                 + 0.04 * torch.nn.functional.cross_entropy(ret["sem_logits_coarse"], labels)
         opt.zero_grad(); loss.backward(); opt.step()
 
+    if a.loss == "intrinsic":
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import torch_losses
+        cluster_target = torch.rand(n, 3, device=dev)
+        target[n // 2:] = (target[:n // 2] + 0.02).clamp(0, 1)          # neighbours: similar colours, as the reference's batches
+        labels = torch.randint(0, a.ssr + 1, (n,), device=dev)            # unshifted: 0 = void
+
+        def istep(hip):
+            ret = r.render_rays(rays)
+            if hip:
+                loss = ssr.ssr_step_loss(ret, target, labels, LOSS_WEIGHTS, cluster_target, semantic=a.ssr > 0)[0]
+            else:
+                levels = [{k: ret[k + t] for k in ("albedo", "shading", "residual", "rgb")} for t in ("_coarse", "_fine")]
+                if a.ssr > 0:
+                    levels[0]["logits"], levels[1]["logits"] = ret["sem_logits_coarse"], ret["sem_logits_fine"]
+                loss = torch_losses.step_loss(levels, target, labels, LOSS_WEIGHTS, cluster_target, semantic=a.ssr > 0)
+            opt.zero_grad(); loss.backward(); opt.step()
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            time_both({"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}, a.iters,
+                      f"SSR training step (C = {a.ssr}), {n} rays x (64+128) samples")
+        sys.exit(0)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         for _ in range(10):
@@ -80,6 +128,29 @@ def step():
     return float(loss.detach()) if False else loss
 
 
+if a.loss == "intrinsic":
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import torch_losses
+    mask = (torch.rand(n, 1, device=dev) > 0.2).float()               # target_m = images[..., -1:] (run_nerf.py:703)
+    cluster_target = torch.rand(n, 3, device=dev)
+    target[n // 2:] = (target[:n // 2] + 0.02).clamp(0, 1)
+
+    def istep(hip):
+        ret = ol.render_rays(rays, net_c, q, 64, retraw=True, perturb=1.0, N_importance=128, network_fine=net_f, white_bkgd=True,
+                             raw_noise_std=0.0)
+        if hip:
+            loss = ol.object_step_loss(ret, target, mask, LOSS_WEIGHTS, cluster_target)[0]
+        else:
+            levels = [{"albedo": ret["albedo0"], "shading": ret["shading0"], "residual": ret["residual0"], "rgb": ret["rgb0"]},
+                      {"albedo": ret["albedo_map"], "shading": ret["shading_map"], "residual": ret["residual_map"], "rgb": ret["rgb_map"]}]
+            loss = torch_losses.step_loss(levels, target, mask, LOSS_WEIGHTS, cluster_target)
+        opt.zero_grad(); loss.backward(); opt.step()
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        time_both({"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}, a.iters,
+                  f"training step (staged path), {n} rays x (64+128) samples")
+    sys.exit(0)
 with warnings.catch_warnings():
     warnings.simplefilter("ignore")
     for _ in range(10):          # the caching allocator needs a few steps to settle on the step's multi-GB blocks (3 warm-ups measured
