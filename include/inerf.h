@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40010
+#define INERF_ABI_VERSION 40011
 
 /* error codes */
 #define INERF_OK              0
@@ -613,6 +613,47 @@ typedef struct inerf_loss_args {
 int64_t inerf_intrinsic_loss_workspace_bytes(int64_t n_rays, int n_levels);
 int inerf_intrinsic_loss(const inerf_loss_args* args, void* stream);
 int inerf_intrinsic_loss_backward(const inerf_loss_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Parameter update: one Adam step of a list of fp32 tensors.
+ * Replaces optimizer.step() of the torch.optim.Adam both trainers build (object_level/run_nerf.py:304,1019;
+ * SSR/training/trainer.py:842,991): weight_decay = 0, amsgrad = False, maximize = False.  Per element, in fp32 with one
+ * rounding per operation (true division, correctly rounded square root - torch's eager single-tensor form):
+ *     m = m + (1 - beta1) * (g - m)          (one fused multiply-add, as ATen's lerp kernels form it)
+ *     v = v * beta2 + ((1 - beta2) * g) * g
+ *     p = p - (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ * with 1 - beta1^t, sqrt(1 - beta2^t) and lr / (1 - beta1^t) formed in fp64 on the device and rounded to fp32 once per
+ * tensor, as the eager path forms them in Python doubles.  t is the tensor's own step count AFTER its increment.
+ *   params, grads, exp_avg, exp_avg_sq, steps: [host] arrays of n_tensors DEVICE pointers; tensor i has counts[i] (> 0)
+ *     contiguous floats and may start on any 4-byte boundary (16-byte accesses are used where the four arrays of a tensor
+ *     share their offset from a 16-byte boundary).  steps[i]: one fp32 on the device per tensor (torch's capturable layout),
+ *     exact up to 2^24; the call advances it by 1.  No two entries may alias.
+ *   counts: [host] array of n_tensors element counts.
+ *   lr: the learning rate, taken in fp32 - unless lr_dev (DEVICE, one fp32) is non-NULL, which then wins: what a captured
+ *     graph needs, since both trainers decay the rate every iteration (run_nerf.py:1024-1027, trainer.py:1006-1009).  Both
+ *     forms are the same arithmetic, so a step launched directly and one replayed from a graph agree bit for bit.
+ *   beta1, beta2 in [0, 1), eps > 0: fp64, as torch holds them (1 - beta is formed in fp64, then rounded).
+ * The pointer table travels in the kernel arguments (no host-to-device copy): 72 tensors per table, a longer list takes
+ * ceil(n_tensors / 72) tables.  Per table two launches: one workgroup advances the step counts, then one streaming launch
+ * updates every tensor of the table (28 B per element; no atomics, no communication between workgroups; bit-identical from run
+ * to run).  Nothing is allocated, synchronised or read on the host; capturable into a HIP graph.
+ * Returns INERF_E_INVALID for a null or misaligned pointer, a non-positive count, a beta outside [0, 1) or eps <= 0 - every
+ * check runs before the first launch - and INERF_OK with nothing launched for n_tensors == 0. */
+typedef struct inerf_adam_args {
+    int32_t n_tensors;
+    float* const* params;
+    const float* const* grads;
+    float* const* exp_avg;
+    float* const* exp_avg_sq;
+    float* const* steps;
+    const int64_t* counts;
+    float lr;
+    const float* lr_dev;
+    double beta1;
+    double beta2;
+    double eps;
+} inerf_adam_args;
+int inerf_adam_step(const inerf_adam_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40010          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40011          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -77,6 +77,14 @@ class LossArgs(C.Structure):
                 ("ce_labels", C.c_void_p), ("weights", C.c_void_p), ("grad_total", C.c_void_p), ("grad_terms", C.c_void_p),
                 ("level", LossLevel * 2), ("state", C.c_void_p), ("state_bytes", C.c_int64)]
 
+
+class AdamArgs(C.Structure):
+    _fields_ = [("n_tensors", C.c_int32), ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("steps", C.c_void_p), ("counts", C.c_void_p), ("lr", C.c_float),
+                ("lr_dev", C.c_void_p), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+ADAM_TABLE_TENSORS = 72      # tensors per launch of inerf_adam_step (its by-value kernel-argument table)
 
 LOSS_KEY_LABELS, LOSS_MASK_OUTER = 1, 2
 LOSS_TERMS, LOSS_STATE_FLOATS, LOSS_MAX_CLASSES = 9, 16, 101
@@ -145,6 +153,7 @@ SYMBOLS = {
     "inerf_intrinsic_loss_workspace_bytes": (_L, [_L, _I]),
     "inerf_intrinsic_loss": (_I, [C.POINTER(LossArgs), _P]),
     "inerf_intrinsic_loss_backward": (_I, [C.POINTER(LossArgs), _P]),
+    "inerf_adam_step": (_I, [C.POINTER(AdamArgs), _P]),
 }
 
 _lib = None

@@ -36,7 +36,8 @@ class GraphedTrainStep:
 
     ``loss_fn(*inputs) -> scalar loss`` renders and compares (device ops only: no ``.item()``, no data-dependent Python
     control flow); ``example_inputs`` fix the shapes - every later batch is copied into static tensors of those shapes.
-    ``optimizer`` must support ``capturable=True`` (torch.optim.Adam, as both trainers use: run_nerf.py:307, trainer.py:841).
+    ``optimizer`` must support ``capturable=True`` (torch.optim.Adam, as both trainers use: run_nerf.py:307, trainer.py:841;
+    ``optim.Adam`` of this package speaks the same protocol - graph B is then the library's own launch).
     The returned loss is a static tensor that the next call overwrites.
     """
 

@@ -29,6 +29,13 @@ becomes ``losses.compute_intrinsic_loss`` where the trainers look it up - ``run_
 trainer.py:15, called at :924,937).  Six scalars in the reference's order through one autograd node; the trainers' weighted
 sums and ``loss.backward()`` stay their own lines.
 
+``--inerf-adam`` (opt-in) replaces the optimizer the trainers build - ``torch.optim.Adam`` at run_nerf.py:304 and trainer.py:842 -
+by ``optim.Adam`` (csrc/adam.hip: one launch of the library per step) over the same parameter groups, with the same
+``lr / betas / eps`` and whatever state a checkpoint loaded into it: ``create_nerf`` in ``run_nerf.py``'s namespace is wrapped
+(it returns the optimizer as its fifth value, run_nerf.py:356, after run_nerf.py:325 loaded the checkpoint) and so is
+``SSRTrainer.create_ssr`` (it assigns ``self.optimizer``, trainer.py:848).  Nothing in ``torch.optim`` is patched; the
+trainers' ``optimizer.zero_grad()``, ``optimizer.step()``, learning-rate decay and ``optimizer.state_dict()`` stay their lines.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -88,12 +95,41 @@ def rebind_cluster_fit(module_name):
 LOSS_SYMBOL = "compute_intrinsic_loss"
 
 
-def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False):
+def _with_inerf_adam_nerf(create_nerf):
+    """``create_nerf`` whose fifth return value (run_nerf.py:356) is ``optim.Adam`` in place of the torch.optim.Adam it built."""
+    import functools
+
+    @functools.wraps(create_nerf)
+    def create_nerf_inerf_adam(*args, **kwargs):
+        from . import optim
+        out = list(create_nerf(*args, **kwargs))
+        out[4] = optim.from_torch(out[4])
+        return tuple(out)
+    return create_nerf_inerf_adam
+
+
+def _with_inerf_adam_ssr(create_ssr):
+    """``create_ssr`` that leaves ``optim.Adam`` in ``self.optimizer`` (trainer.py:848)."""
+    import functools
+
+    @functools.wraps(create_ssr)
+    def create_ssr_inerf_adam(self, *args, **kwargs):
+        from . import optim
+        out = create_ssr(self, *args, **kwargs)
+        self.optimizer = optim.from_torch(self.optimizer)
+        return out
+    return create_ssr_inerf_adam
+
+
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
     names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ()) + ((LOSS_SYMBOL,) if losses else ())
     for name in names:
         namespace[name] = getattr(object_level, name)
+    if adam:
+        namespace["create_nerf"] = _with_inerf_adam_nerf(namespace["create_nerf"])
+        names = names + ("create_nerf",)
     if cluster_fit:
         rebind_cluster_fit("cluster")                  # run_nerf.py:24 `from cluster import Cluster, Cluster_Manager`
     if with_render_path and "Cluster_Manager" in namespace:
@@ -106,7 +142,7 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     bound = {}
@@ -140,10 +176,12 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False):
     if losses:                                         # trainer.py:15 holds the function by value; step() looks it up in its module
         setattr(trainer, LOSS_SYMBOL, getattr(ssr, LOSS_SYMBOL))
         bound.setdefault("SSR.training.trainer", []).append(LOSS_SYMBOL)
+    if adam:                                           # (create_ssr is the mixin's by now: the wrapper goes around that one)
+        trainer.SSRTrainer.create_ssr = _with_inerf_adam_ssr(trainer.SSRTrainer.create_ssr)
     return bound
 
 
-def prepare(script, with_render_path=False, cluster_fit=False, losses=False):
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -157,10 +195,10 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False):
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam)
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam)
     return mod, main
 
 
@@ -175,6 +213,9 @@ def main(argv=None):
     losses = "--inerf-losses" in argv
     if losses:
         argv.remove("--inerf-losses")
+    adam = "--inerf-adam" in argv
+    if adam:
+        argv.remove("--inerf-adam")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -182,7 +223,10 @@ def main(argv=None):
     from . import _capi
     _capi.lib()                                        # fail now, and loudly, if the HIP library is missing
     # (positional as before for the first two; the loss flag only when given, so a two-flag `prepare` stand-in keeps working)
-    mod, main_code = prepare(script, with_render_path, cluster_fit, losses) if losses else prepare(script, with_render_path, cluster_fit)
+    if adam:                                           # (by keyword and only when given, for the same reason)
+        mod, main_code = prepare(script, with_render_path, cluster_fit, losses, adam=True)
+    else:
+        mod, main_code = prepare(script, with_render_path, cluster_fit, losses) if losses else prepare(script, with_render_path, cluster_fit)
     sys.argv = [script] + argv[1:]                     # the script's own argument parser sees its own command line
     mod.__dict__["__name__"] = "__main__"
     exec(main_code, mod.__dict__)

@@ -2,10 +2,12 @@
 """Training-step timing through the object-level front-end (staged path: HIP sampling / compositing with HIP backward,
 network layers through torch autograd) and the compositing kernels' HBM rates.
 
-    python scripts/bench_train_step.py [--rays 2048] [--iters 10] [--ssr C] [--loss intrinsic]
+    python scripts/bench_train_step.py [--rays 2048] [--iters 10] [--ssr C] [--loss intrinsic] [--optimizer inerf]
 ``--loss intrinsic`` times the step with the loss the reference trains with (compute_intrinsic_loss on both levels, image and
 cluster MSE, the SSR cross-entropy) instead of the default stand-in loss - once as torch expressions (scripts/torch_losses.py)
 and once on the two launches of csrc/losses.hip, alternating in the same process.
+``--optimizer inerf`` (with ``--loss intrinsic``) adds a third step to that alternation: the HIP loss with ``optim.Adam``
+(csrc/adam.hip) in place of torch.optim.Adam over the same parameters - the step next to it is its parent figure on the same box.
 The batch is the reference's: N_rand = 1024 rays plus one neighbour each (run_nerf.py:918-929), 64 + 128 samples.
 """
 import argparse
@@ -27,7 +29,10 @@ ap.add_argument("--rays", type=int, default=2048)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--ssr", type=int, default=-1, help="C >= 0: the SSR network with C classes through ssr.SSRRenderer instead")
 ap.add_argument("--loss", choices=("mse", "intrinsic"), default="mse", help="intrinsic: the reference's full loss, as torch expressions and in HIP")
+ap.add_argument("--optimizer", choices=("torch", "inerf"), default="torch", help="inerf: also time the step with optim.Adam (needs --loss intrinsic)")
 a = ap.parse_args()
+if a.optimizer == "inerf" and a.loss != "intrinsic":
+    raise SystemExit("--optimizer inerf is timed next to torch.optim.Adam inside the --loss intrinsic alternation")
 LOSS_WEIGHTS = {"image": 1.0, "chroma": 1.0, "sparsity": 0.01, "far": 0.01, "shading": 1.0, "residual": 1.0, "intensity": 0.1, "cluster": 1.0,
                 "semantic": 0.04}
 
@@ -78,7 +83,7 @@ if a.ssr >= 0:          # trainer.py:876-991: 1024 rays (512 + neighbours), dept
         target[n // 2:] = (target[:n // 2] + 0.02).clamp(0, 1)          # neighbours: similar colours, as the reference's batches
         labels = torch.randint(0, a.ssr + 1, (n,), device=dev)            # unshifted: 0 = void
 
-        def istep(hip):
+        def istep(hip, opt=opt):
             ret = r.render_rays(rays)
             if hip:
                 loss = ssr.ssr_step_loss(ret, target, labels, LOSS_WEIGHTS, cluster_target, semantic=a.ssr > 0)[0]
@@ -91,7 +96,12 @@ if a.ssr >= 0:          # trainer.py:876-991: 1024 rays (512 + neighbours), dept
 
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            time_both({"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}, a.iters,
+            steps = {"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}
+            if a.optimizer == "inerf":
+                from intrinsicnerf_amd import optim
+                opt_inerf = optim.Adam(list(r.ssr_net_coarse.parameters()) + list(r.ssr_net_fine.parameters()), lr=5e-4)
+                steps["HIP launches + optim.Adam"] = lambda: istep(True, opt_inerf)
+            time_both(steps, a.iters,
                       f"SSR training step (C = {a.ssr}), {n} rays x (64+128) samples")
         sys.exit(0)
     with warnings.catch_warnings():
@@ -135,7 +145,7 @@ if a.loss == "intrinsic":
     cluster_target = torch.rand(n, 3, device=dev)
     target[n // 2:] = (target[:n // 2] + 0.02).clamp(0, 1)
 
-    def istep(hip):
+    def istep(hip, opt=opt):
         ret = ol.render_rays(rays, net_c, q, 64, retraw=True, perturb=1.0, N_importance=128, network_fine=net_f, white_bkgd=True,
                              raw_noise_std=0.0)
         if hip:
@@ -148,7 +158,12 @@ if a.loss == "intrinsic":
 
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        time_both({"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}, a.iters,
+        steps = {"torch expressions": lambda: istep(False), "HIP launches": lambda: istep(True)}
+        if a.optimizer == "inerf":
+            from intrinsicnerf_amd import optim
+            opt_inerf = optim.Adam(list(net_c.parameters()) + list(net_f.parameters()), lr=5e-4)
+            steps["HIP launches + optim.Adam"] = lambda: istep(True, opt_inerf)
+        time_both(steps, a.iters,
                   f"training step (staged path), {n} rays x (64+128) samples")
     sys.exit(0)
 with warnings.catch_warnings():
