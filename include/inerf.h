@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40011
+#define INERF_ABI_VERSION 40012
 
 /* error codes */
 #define INERF_OK              0
@@ -48,6 +48,18 @@ extern "C" {
 #define INERF_FLAG_LINDISP      2u   /* run_nerf.py:467-468 (object-level only)                           */
 #define INERF_FLAG_ENDPOINT     4u   /* SSR endpoint_feat: fine raw carries the 128-d views activation    */
 #define INERF_FLAG_U_PER_RAY    8u   /* `u` is [N, n_importance] (random) instead of a shared [n_importance] */
+/* inerf_encode_mlp*: run the colour heads only on sample points with positive density.  raw2outputs (run_nerf.py:359-412) forms
+ * alpha = 1 - exp(-relu(sigma) * dist), so a point with sigma <= 0 has weight +0 and its colours enter every map as 0 * finite.
+ * With the flag such a point's raw row is (0, 0, 0, sigma, 0, 0, 0, 0, 0, 0, 0); a point with !(sigma <= 0) - a NaN included - has
+ * the row of the ungated call, bit for bit.  Honoured for the object-level network in INERF_PREC_F16X3 without the endpoint
+ * feature, and only with a workspace (inerf_encode_mlp_workspace_bytes with the flag: the survivors' records, bounded by
+ * INERF_GATE_BYTES, default 2 GiB; inerf_encode_mlp, which has none, returns INERF_E_WORKSPACE); every other configuration runs
+ * the ungated kernel.  inerf_render_rays sets it by itself for a pass whose raw tensor the caller does not receive
+ * (raw_coarse / raw_fine NULL) and whose noise tensor is NULL (noise is added to sigma before the ReLU); INERF_GATE=0 in the
+ * environment turns that off.  The maps are those of the ungated path (a zero-weight term may flip the sign of a zero sum).
+ * ONE deviation: a gated point's heads are not evaluated, so they can neither raise INERF_STATUS_F16_RANGE nor turn a
+ * zero-weight term into NaN - either would take a non-finite head activation on a point whose trunk is finite. */
+#define INERF_FLAG_GATE_COLOUR 32u
 
 /* arithmetic of the MLP GEMMs (inerf_net_desc.precision) */
 #define INERF_PREC_F32        0   /* v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation             */

@@ -10,13 +10,14 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40011          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40012          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
 PREC_F32, PREC_F16X3 = 0, 1
 STATUS_F16_RANGE = 1
 FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_ENDPOINT, FLAG_U_PER_RAY, FLAG_BINS_DIRECT = 1, 2, 4, 8, 16
+FLAG_GATE_COLOUR = 32         # inerf_encode_mlp*: colour heads only on points with positive density (include/inerf.h)
 CLUSTER_IGNORE_LABEL = 1
 CAM_OPENGL = 1
 BASE_CHANNELS, ENDPOINT_DIM, RAY_FLOATS, MAX_CLASSES = 11, 128, 11, 240

@@ -3,6 +3,7 @@
 // (SSR/training/trainer.py:717-808).  No host synchronisation, no allocation: all scratch lives in
 // the caller's workspace.
 #include <cstdint>
+#include <cstdlib>
 
 #include "layout.h"
 
@@ -20,6 +21,13 @@ struct Plan {
 // raw is by far the largest (N x S x CH floats: ~6 GB for 32768 rays x 192 samples x 240 channels), and the SSR
 // front-end asks for raw_coarse / raw_fine by default.
 enum : unsigned { kHaveZc = 1, kHaveWc = 2, kHaveRawC = 4, kHaveZs = 8, kHaveZf = 16, kHaveRawF = 32 };
+
+// Colour heads only on points with positive density (INERF_FLAG_GATE_COLOUR): a pass is gated when nobody outside the library sees its raw
+// tensor and no noise is added to its sigma; which networks the flag does anything for is inerf_encode_mlp*'s business.  INERF_GATE=0: never.
+uint32_t gate_flag(bool raw_provided, bool noise) {
+    const char* e = std::getenv("INERF_GATE");
+    return (raw_provided || noise || (e && e[0] == '0')) ? 0u : INERF_FLAG_GATE_COLOUR;
+}
 
 unsigned provided(const inerf_render_args& a) {
     return (a.z_coarse ? kHaveZc : 0u) | (a.coarse.weights ? kHaveWc : 0u) | (a.raw_coarse ? kHaveRawC : 0u) |
@@ -46,9 +54,11 @@ Plan plan(const inerf_net_desc& net, int64_t n, int sc, int ni, uint32_t flags, 
         p.z_f = take(n * p.s_f, kHaveZf);
         p.raw_f = take(n * p.s_f * p.ch_f, kHaveRawF);
     }
-    // scratch of the encode+MLP launches (the SSR network's channel-split semantic head); one region serves both passes
-    const int64_t ws_c = inerf_encode_mlp_workspace_bytes(&net, n, sc, flags & ~INERF_FLAG_ENDPOINT);
-    const int64_t ws_f = ni > 0 ? inerf_encode_mlp_workspace_bytes(&net, n, p.s_f, flags) : 0;
+    // scratch of the encode+MLP launches (the SSR network's channel-split semantic head; the density gate's records - reserved whenever the
+    // caller does not take the pass's raw tensor: whether noise keeps the gate off is only known at the call); one region serves both passes
+    const uint32_t mlp_flags = flags & ~INERF_FLAG_GATE_COLOUR;
+    const int64_t ws_c = inerf_encode_mlp_workspace_bytes(&net, n, sc, (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(have & kHaveRawC, false));
+    const int64_t ws_f = ni > 0 ? inerf_encode_mlp_workspace_bytes(&net, n, p.s_f, mlp_flags | gate_flag(have & kHaveRawF, false)) : 0;
     p.mlp_ws_bytes = ws_c > ws_f ? ws_c : ws_f;
     p.mlp_ws = off;
     off += up(p.mlp_ws_bytes);
@@ -91,8 +101,10 @@ extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) {
     if (rc) return rc;
     float* raw_c = a->raw_coarse ? a->raw_coarse : f(p.raw_c);
     // the coarse net never emits the endpoint feature (trainer.py:751-755: endpoint_feat=False)
-    rc = inerf_encode_mlp_chunked(&a->net, a->packed_coarse, a->rays, z_c, n, sc, a->flags & ~INERF_FLAG_ENDPOINT, raw_c, a->status, a->status_rays,
-                             ws + p.mlp_ws, p.mlp_ws_bytes, stream);
+    const uint32_t mlp_flags = a->flags & ~INERF_FLAG_GATE_COLOUR;
+    rc = inerf_encode_mlp_chunked(&a->net, a->packed_coarse, a->rays, z_c, n, sc,
+                                  (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr), raw_c, a->status,
+                                  a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
     if (rc) return rc;
     inerf_composite_out oc = a->coarse;
     oc.feat = nullptr;
@@ -108,7 +120,8 @@ extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) {
     if (rc) return rc;
     float* raw_f = a->raw_fine ? a->raw_fine : f(p.raw_f);
     const float* w_fine = a->packed_fine ? a->packed_fine : a->packed_coarse;   // run_nerf.py:506
-    rc = inerf_encode_mlp_chunked(&a->net, w_fine, a->rays, z_f, n, p.s_f, a->flags, raw_f, a->status, a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
+    rc = inerf_encode_mlp_chunked(&a->net, w_fine, a->rays, z_f, n, p.s_f, mlp_flags | gate_flag(a->raw_fine != nullptr, a->noise_fine != nullptr), raw_f,
+                                  a->status, a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
     if (rc) return rc;
     const bool ep = ssr && (a->flags & INERF_FLAG_ENDPOINT);
     inerf_composite_out of = a->fine;

@@ -406,31 +406,41 @@ int launch_mlp_f32(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream)
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch = nullptr, int64_t status_rays = 0);
+                           float* sem_scratch = nullptr, int64_t status_rays = 0, void* gate_ws = nullptr);
+
+// workspace of a launch: the kernels' scratch (sem_scratch_bytes), then - 256-byte aligned - the density gate's buffers
+static bool gated(const inerf_net_desc& net, uint32_t flags) { return (flags & INERF_FLAG_GATE_COLOUR) && inerf::mlp_gate_applies(net, flags); }
+static int64_t scratch_bytes(const inerf_net_desc& net, int64_t n_rays, int n_samples, uint32_t flags) {
+    const int64_t b = inerf::sem_scratch_bytes(net, n_rays * (int64_t)n_samples, (flags & INERF_FLAG_ENDPOINT) != 0);
+    return gated(net, flags) ? (b + 255) / 256 * 256 : b;
+}
+static int64_t workspace_need(const inerf_net_desc& net, int64_t n_rays, int n_samples, uint32_t flags) {
+    return scratch_bytes(net, n_rays, n_samples, flags) + (gated(net, flags) ? inerf::mlp_gate_plan(n_rays, n_samples).bytes : 0);
+}
 
 extern "C" int64_t inerf_encode_mlp_workspace_bytes(const inerf_net_desc* net, int64_t n_rays, int n_samples, uint32_t flags) {
     if (!net || !inerf::net_supported(*net) || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
-    return inerf::sem_scratch_bytes(*net, n_rays * (int64_t)n_samples, (flags & INERF_FLAG_ENDPOINT) != 0);
+    return workspace_need(*net, n_rays, n_samples, flags);
 }
 
 extern "C" int inerf_encode_mlp_ws(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                                    int n_samples, uint32_t flags, float* raw_out, int32_t* status, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
     if (!net || !inerf::net_supported(*net) || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
-    const int64_t need = inerf::sem_scratch_bytes(*net, n_rays * (int64_t)n_samples, (flags & INERF_FLAG_ENDPOINT) != 0);
+    const int64_t need = workspace_need(*net, n_rays, n_samples, flags), scratch = scratch_bytes(*net, n_rays, n_samples, flags);
     if (need > 0 && (!workspace || workspace_bytes < need)) return INERF_E_WORKSPACE;
     return encode_mlp_impl(net, packed, rays, z, n_rays, n_samples, flags, raw_out, nullptr, nullptr, status, stream,
-                           need > 0 ? static_cast<float*>(workspace) : nullptr);
+                           scratch > 0 ? static_cast<float*>(workspace) : nullptr, 0, need > scratch ? static_cast<char*>(workspace) + scratch : nullptr);
 }
 
 extern "C" int inerf_encode_mlp_chunked(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                                         int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays, void* workspace,
                                         int64_t workspace_bytes, void* stream) {
     if (!net || !inerf::net_supported(*net) || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
-    const int64_t need = inerf::sem_scratch_bytes(*net, n_rays * (int64_t)n_samples, (flags & INERF_FLAG_ENDPOINT) != 0);
+    const int64_t need = workspace_need(*net, n_rays, n_samples, flags), scratch = scratch_bytes(*net, n_rays, n_samples, flags);
     if (need > 0 && (!workspace || workspace_bytes < need)) return INERF_E_WORKSPACE;
     return encode_mlp_impl(net, packed, rays, z, n_rays, n_samples, flags, raw_out, nullptr, nullptr, status, stream,
-                           need > 0 ? static_cast<float*>(workspace) : nullptr, status_rays);
+                           scratch > 0 ? static_cast<float*>(workspace) : nullptr, status_rays, need > scratch ? static_cast<char*>(workspace) + scratch : nullptr);
 }
 
 extern "C" int inerf_encode_mlp(const inerf_net_desc* net, const float* packed, const float* rays, const float* z,
@@ -468,7 +478,7 @@ extern "C" int inerf_encode_mlp_train(const inerf_net_desc* net, const float* pa
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch, int64_t status_rays) {
+                           float* sem_scratch, int64_t status_rays, void* gate_ws) {
     using namespace inerf;
     if (net && n_rays == 0) return net_supported(*net) ? INERF_OK : INERF_E_UNSUPPORTED;      // empty batch: pointers may be null
     if (!net || !packed || !rays || !z || !raw_out || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
@@ -477,7 +487,7 @@ static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const
     const int64_t n_points = n_rays * (int64_t)n_samples;
     if (n_points >= (int64_t)1 << 31) return INERF_E_UNSUPPORTED;     // caller chunks (the front-ends do)
     const bool ssr = net->variant == INERF_VARIANT_SSR;
-    MlpParams p;
+    MlpParams p{};
     p.wts = packed; p.rays = rays; p.z = z; p.raw = raw_out; p.status = status;
     p.status_rays = (status && status_rays > 0 && status_rays < n_rays) ? (int)status_rays : 0;      // (>= n_rays: everything in word 0)
     p.save = save;
@@ -493,6 +503,10 @@ static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const
     p.n_classes = ssr ? net->n_classes : 0;
     p.channels = INERF_BASE_CHANNELS + p.n_classes + (p.endpoint ? INERF_ENDPOINT_DIM : 0);
     p.l_xyz = net->l_xyz; p.l_dir = net->l_dir; p.xyz_div = net->xyz_div;
+    if (!save && gated(*net, flags)) {      // colour heads only on points with positive density (include/inerf.h INERF_FLAG_GATE_COLOUR)
+        if (!gate_ws) return INERF_E_WORKSPACE;
+        return launch_mlp_f16x3_gated(p, n_rays, gate_ws, (hipStream_t)stream);
+    }
     return net->precision == INERF_PREC_F16X3 ? launch_mlp_f16x3(p, n_points, ssr, (hipStream_t)stream)
                                               : launch_mlp_f32(p, n_points, ssr, (hipStream_t)stream);
 }

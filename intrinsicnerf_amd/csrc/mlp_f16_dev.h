@@ -287,8 +287,8 @@ __device__ __forceinline__ float flag_f16_range(const MlpParams& p, int first_po
         if (p.status_rays > 0) {
             int last = first_point + tile_points - 1;
             last = last < p.n_points ? last : p.n_points - 1;
-            w0 = (first_point / p.n_samples) / p.status_rays;
-            w1 = (last / p.n_samples) / p.status_rays;
+            w0 = (p.ray0 + first_point / p.n_samples) / p.status_rays;
+            w1 = (p.ray0 + last / p.n_samples) / p.status_rays;
         }
         for (int w = w0; w <= w1; ++w) atomicOr(p.status + w, INERF_STATUS_F16_RANGE);
     }

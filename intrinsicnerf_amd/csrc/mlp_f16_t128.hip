@@ -14,9 +14,11 @@
 // that true for the two heads whose hidden layers stay in registers (albedo | shading hidden, view-dependent hidden: their
 // output sums are formed per 64- / 32-channel group, in group order), those two layers keep the 64-point kernel's wave tile -
 // channel group w8 & 3 x point half w8 >> 2 - and stream their weights twice per tile (15 % of the FLOPs).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "mlp_f16_dev.h"
 #include "mlp_f16_heads.h"
@@ -62,10 +64,25 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 // of a fragment, one of the two mask words of a lane), so the chain and the weight-gradient kernels read either forward's buffer.
 // kPipe (object-level inference, INERF_F16_KERNEL=pp): the trunk as a software pipeline over the tile's two 64-point halves - each half's
 // epilogue is issued between the MFMAs of the other half's GEMM (mlp_f16_pp.h).  Same values, same summation order: bit-identical results.
-template <bool kSsr, bool kSave = false, bool kPipe = false>
-__global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParams p) {
+//
+// kMode (density gate, object-level inference: DESIGN.md 3.1c) - the ONE tile body serves three kernels, so the gated pair computes
+// with the same instructions in the same order as the whole kernel:
+//   kWhole      encode, trunk, heads: everything of a tile, as above
+//   kGateTrunk  encode, trunk, then only sigma: raw[pt] = (0, 0, 0, sigma, 0 ...).  A point SURVIVES when !(sigma <= 0) (a NaN survives);
+//               the tile's survivors are counted by ballot, one lane reserves their contiguous record range with one atomicAdd on
+//               MlpParams.gate_count, and each survivor's h7 row leaves exactly as the epilogue left it in the planes (256 f16 hi |
+//               256 f16 lo = 1 KB, sixteen-byte stores) together with its point index
+//   kGateHeads  walks ceil(*gate_count / 128) tiles of records: rows back into the planes, the direction encoding again from point
+//               index -> ray, then the heads; the ten colour channels go to raw[index].  Rows past the count are computed on the last
+//               record and not stored.  The range guard is per POINT here (a tile holds points of rays from anywhere in the launch).
+enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2 };
+constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
+
+template <bool kSsr, bool kSave, bool kPipe, int kMode>
+__device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     static_assert(!(kSsr && kSave), "the saving form is the object-level network's");
     static_assert(!kPipe || (!kSsr && !kSave), "the pipelined trunk is the object-level inference form");
+    static_assert(kMode == kWhole || (!kSsr && !kSave && !kPipe), "the density gate is the object-level inference form's");
     constexpr int kParts = 512 / kPtsT;
     // the wide GEMMs' first products take a zero C operand instead of 64 v_mov in front of every GEMM (wide_gemm_h PEEL): +1.3 % same-box,
     // same bits (profiles/r06_peel_ab.txt); the saving form keeps the explicit zeroing like the two-workgroup one
@@ -91,12 +108,23 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
 
     WidePreH<1> pre1;
     WidePreH<2> pre2;
-    prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
+    if constexpr (kMode == kGateHeads) prefetch_w<2>(pre2, wb, frag256(L.as1, 16));
+    else                               prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
+    // gated heads: the survivor count of this sub-launch (written by the trunk kernel in front of it on the stream; never more than its points)
+    int n_rec = 0;
+    if constexpr (kMode == kGateHeads) {
+        n_rec = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<const volatile unsigned*>(p.gate_count));
+        n_rec = n_rec < p.n_points ? n_rec : p.n_points;
+    }
+    const int n_tiles = kMode == kGateHeads ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
+    // the 16 pad bytes behind a row's direction columns (hi plane; no GEMM uses what it reads there).  Gated trunk: rows 0..7 hold the
+    // waves' survivor counts, row 8 the tile's first record.  Gated heads: row r holds four words, non-zero when point r left the f16 range
+    auto pad_of = [&](int r) { return reinterpret_cast<int*>(ldst + r * kRowD + kWidth + kDirCols); };
     float amax = 0.0f;                            // running maxima of |scaled value| (encoder inputs / layer outputs): the f16 range guard
     f16x2 amax2 = {(_Float16)0.0f, (_Float16)0.0f};
     const int n_tiles64 = (p.n_points + kTilePoints - 1) / kTilePoints;      // the save slots' tiles
 
-    for (int tile = blockIdx.x; tile < p.n_tiles; tile += gridDim.x) {
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         int lane_t = tid;                         // (laundered per tile: keeps the lane_t parts of per-tile offsets out of the loop-invariant set,
         asm volatile("" : "+v"(lane_t));          // and `lane_t` itself out of the registers that live across the tile loop)
         lane_t &= 63;
@@ -110,33 +138,36 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             asm volatile("" : "+v"(tid_o));
             const int pt = tid_o % kPtsT, part = tid_o / kPtsT;
             int gp = tile * kPtsT + pt;
+            if constexpr (kMode == kGateHeads) gp = p.gate_idx[gp < n_rec ? gp : n_rec - 1];      // the record's point
             gp = gp < p.n_points ? gp : p.n_points - 1;
             int n_samples = p.n_samples;           // (laundered: the division's reciprocal, as a loop invariant, is one more register held - and
             asm volatile("" : "+s"(n_samples));    // at this kernel's 256 spilled - across the whole tile)
             const int ray = gp / n_samples;
             const float* __restrict__ r = p.rays + (size_t)ray * INERF_RAY_FLOATS;
-            const float zz = __builtin_nontemporal_load(p.z + gp);
             _Float16* row = ldst + pt * kRowD;
-            float x[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));                                // run_nerf.py:488
-                if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);              // semantic_nerf.py:64
-            }
-            for (int f = part; f < p.l_xyz; f += kParts) {
-                const float s = (float)(1 << f);
+            if constexpr (kMode != kGateHeads) {      // (the gated heads' rows arrive with h7 in these columns)
+                const float zz = __builtin_nontemporal_load(p.z + gp);
+                float x[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    float sn, cs;
-                    fast_sincosf(x[c] * s, &sn, &cs);
-                    split_store<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
-                    split_store<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
+                    x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));                                // run_nerf.py:488
+                    if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);              // semantic_nerf.py:64
                 }
-            }
-            if (part == 2) {
+                for (int f = part; f < p.l_xyz; f += kParts) {
+                    const float s = (float)(1 << f);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) split_store<kPlaneT>(row + c, x[c], amax);
-                for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) { row[c] = (_Float16)0.0f; row[kPlaneT + c] = (_Float16)0.0f; }
+                    for (int c = 0; c < 3; ++c) {
+                        float sn, cs;
+                        fast_sincosf(x[c] * s, &sn, &cs);
+                        split_store<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
+                        split_store<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
+                    }
+                }
+                if (part == 2) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) split_store<kPlaneT>(row + c, x[c], amax);
+                    for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) { row[c] = (_Float16)0.0f; row[kPlaneT + c] = (_Float16)0.0f; }
+                }
             }
             if (with_dir) {
                 const int fd = kParts - 1 - part;
@@ -156,14 +187,32 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
                     for (int c = 3 + 6 * p.l_dir; c < kDirCols; ++c) { row[kColDirD + c] = (_Float16)0.0f; row[kPlaneT + kColDirD + c] = (_Float16)0.0f; }
                 }
             }
+            if constexpr (kMode == kGateHeads) {      // this thread's word of the point's range flags: written by every tile, so never stale
+                pad_of(pt)[part] = !(amax <= kF16Safe);
+                amax = 0.0f;
+            }
         };
+        if constexpr (kMode == kGateHeads) {
+            // this wave's sixteen rows (the rows its own lanes read last in the tile before: no barrier needed in front), a whole 1 KB
+            // record per instruction: lane = sixteen-byte piece, pieces 0..31 the hi plane's columns, 32..63 the lo plane's
+            u32x4 v[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                int rec = tile * kPtsT + 16 * wave + j;
+                rec = rec < n_rec ? rec : n_rec - 1;
+                v[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p.gate_rec + (size_t)rec * kGateRecordBytes) + lane_t);
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                *reinterpret_cast<u32x4*>(ldst + (lane_t >> 5) * kPlaneT + (16 * wave + j) * kRowD + 8 * (lane_t & 31)) = v[j];
+        }
 #ifdef INERF_ABL_NO_ENCODE      // (timing ablation of a development build: the first tile's encoding stays in LDS; results are wrong)
         if (tile == (int)blockIdx.x)
 #endif
         encode(true);
         __syncthreads();
         // park the encoding for the skip layer (piece q = tid + 512 i of the tile's 2 048 sixteen-byte pieces: plane q / 1024, row (q % 1024) / 8)
-        const bool enc_cached = !kSsr && !kSave && p.sem_scratch != nullptr;
+        const bool enc_cached = !kSsr && !kSave && kMode != kGateHeads && p.sem_scratch != nullptr;
         const __amdgpu_buffer_rsrc_t enc_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             p.sem_scratch, 0, enc_cached ? (int)((unsigned)gridDim.x * (unsigned)kEncCacheBytesT) : 0, 0x00020000);
         auto enc_piece = [&](int i) {
@@ -258,7 +307,9 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
         auto pf256 = [&](const GemmSlot& s, int kbt) { return [&, kbt]() { prefetch_w<2>(pre2, wb, frag256(s, kbt)); }; };
 
         // ---------------- trunk ----------------
-        if constexpr (kPipe) {
+        if constexpr (kMode == kGateHeads) {
+            // (h7 came with the records)
+        } else if constexpr (kPipe) {
             // halves A (rows 0..63) and B (rows 64..127); accX: the half's accumulators of its latest GEMM, epilogued during the other half's next one
             f32x16 accA[2], accB[2];
             f32x4 bias[1][4];                      // of the layer whose epilogue the next step carries (requested a barrier + a k-block ahead)
@@ -332,15 +383,82 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[6], 16), xr, 0, 0, lane_t, am1);
             store256(L.trunk[6], true, SAVE_H0 + 6, pf32(L.trunk[7], 16), kWithBits);
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[7], 16), xr, 0, 0, lane_t, am1);
-            store256(L.trunk[7], true, SAVE_H7, pf256(L.as1, 16), kWithBits);
+            if constexpr (kMode == kGateTrunk) store256(L.trunk[7], true, SAVE_H7, pf32(L.trunk[0], 4), kWithBits);
+            else                               store256(L.trunk[7], true, SAVE_H7, pf256(L.as1, 16), kWithBits);
+        }
 
+        // ---------------- density gate: sigma, the raw rows, the survivors' records ----------------
+        if constexpr (kMode == kGateTrunk) {
+            const int pt16 = tile * kPtsT + 16 * wave;
+            const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
+            const float sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];   // lanes 0..15: this wave's points
+            const bool keep = lane_t < 16 && pt16 + lane_t < p.n_points && !(sigma <= 0.0f);
+            const unsigned kept = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep));
+            if (lane_t == 0) pad_of(wave)[0] = __popc(kept);
+            // raw: the wave's 16 points x 11 floats as 44 sixteen-byte pieces (like the whole kernel's), sigma in channel 3 of zeros
+            float piece[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = 4 * (lane_t < 44 ? lane_t : 43) + i, pt = e / INERF_BASE_CHANNELS;
+                const float s_pt = __shfl(sigma, pt);
+                piece[i] = e - INERF_BASE_CHANNELS * pt == 3 ? s_pt : 0.0f;
+            }
+            if (p.channels == INERF_BASE_CHANNELS && pt16 + 16 <= p.n_points && (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0) {
+                if (lane_t < 44)
+                    __builtin_nontemporal_store(f32x4{piece[0], piece[1], piece[2], piece[3]},
+                                                reinterpret_cast<f32x4*>(p.raw + (size_t)pt16 * INERF_BASE_CHANNELS) + lane_t);
+            } else if (lane_t < 16 && pt16 + lane_t < p.n_points) {
+                float* const out_row = p.raw + (size_t)(pt16 + lane_t) * p.channels;
+#pragma unroll
+                for (int c = 0; c < INERF_BASE_CHANNELS; ++c) __builtin_nontemporal_store(c == 3 ? sigma : 0.0f, out_row + c);
+            }
+            __syncthreads();                       // the eight counts are there
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                const int c = pad_of(w)[0];
+                total += c;
+                before += w < wave ? c : 0;
+            }
+            if (tid == 0) pad_of(8)[0] = total > 0 ? (int)atomicAdd(p.gate_count, (unsigned)total) : 0;
+            __syncthreads();
+            const int slot0 = __builtin_amdgcn_readfirstlane(pad_of(8)[0] + before);      // (<= the launch's points - this wave's survivors: inside the buffers)
+            if (keep) p.gate_idx[slot0 + __popc(kept & ((1u << lane_t) - 1u))] = pt16 + lane_t;
+            int slot = slot0;
+            for (unsigned m = kept; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
+                const int j = __builtin_ctz(m);
+                const u32x4 v = *reinterpret_cast<const u32x4*>(ldst + (lane_t >> 5) * kPlaneT + (16 * wave + j) * kRowD + 8 * (lane_t & 31));
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p.gate_rec + (size_t)slot * kGateRecordBytes) + lane_t);
+            }
+            flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
+            __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
+            continue;
         }
 
         // ---------------- heads ----------------
         const bool sem = kSsr && L.sem_rbs > 0;
+        // (gated heads: the row's record, whose point is looked up where the row is written)
         const int my_pt = tile * kPtsT + 16 * wave + (lane_t & 15);
-        const bool my_valid = my_pt < p.n_points;
-        float* const out_row = p.raw + (size_t)(my_valid ? my_pt : 0) * p.channels;
+        const bool my_valid = my_pt < (kMode == kGateHeads ? n_rec : p.n_points);
+        float* const out_row = p.raw + (size_t)(my_valid && kMode != kGateHeads ? my_pt : 0) * p.channels;
+        // gated heads, the per-point range guard: every check is of ONE layer (amax2 starts from zero again behind it), and only a wave
+        // that saw a value out of range looks up which of its lanes' points it belongs to - from the hi halves themselves, which are
+        // what amax2 is the maximum of
+        auto out_of_range = [&]() { return __any(!((float)amax2[0] <= kF16Safe) || !((float)amax2[1] <= kF16Safe)) != 0; };
+        auto flag_operands = [&](const auto& hi_ops) {      // register operands [q][pb]: point (lane & 31) of point block pb of half ph
+            if (out_of_range()) {
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb) {
+                    bool bad = false;
+#pragma unroll
+                    for (int q = 0; q < (int)std::extent_v<std::remove_reference_t<decltype(hi_ops)>>; ++q)
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) bad |= !(fabsf((float)hi_ops[q][pb][i]) <= kF16Safe);
+                    if (bad) pad_of((lane_t & 31) + 32 * pb + 64 * ph)[0] = 1;
+                }
+            }
+            amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
+        };
         // (operand addresses of the heads from the per-tile laundered lane_t index: as loop invariants they are two more spilled registers)
         const _Float16* const xs = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);   // skinny operand reads: this wave's 16 points
 
@@ -356,7 +474,9 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             if (sem) prefetch_w<1>(pre1, wb, frag128(L.sem1, 16));
             else     prefetch_w<1, 4096>(pre1, wb, frag32(L.feat, 16));
             f16x8 hi[4][2], lo[4][2];
+            if constexpr (kMode == kGateHeads) amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
             to_operands<2, false, 2, !kSave>(am2, inv2, bias2, amax2, hi, lo);
+            if constexpr (kMode == kGateHeads) flag_operands(hi);
             if constexpr (kSave) {                // the hidden layer as operand fragments, transposed out of the registers (it never touches LDS):
                 int lane_o = lane_t;              // channel group cg of point half ph = the 64-point kernel's wave cg of tile 2 * tile + ph
                 asm volatile("" : "+v"(lane_o));
@@ -394,18 +514,36 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
         // feature (no activation) in place of h7, then the view-dependent layer over [feature | dir] -> registers
         wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.feat, 16), xr, 0, 0, lane_t, am1);
         // sigma, last of h7's readers (here, not in front of the heads: four registers fewer across their GEMM loops)
-        const f32x4 sig4 = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs, lane_t);
+        f32x4 sig4 = {0.0f, 0.0f, 0.0f, 0.0f};      // (gated heads: the trunk kernel wrote sigma)
+        if constexpr (kMode != kGateHeads) sig4 = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs, lane_t);
         {
             WidePreH<1> prev;
             store256(L.feat, false, SAVE_FEAT, [&]() { prefetch_w<1>(prev, wb, frag128(L.views, 18)); }, kNoBits);
+            if constexpr (kMode == kGateHeads) {      // this wave's 32 feature channels of its lanes' four points, complete in the planes behind the barrier
+                if (out_of_range()) {
+#pragma unroll
+                    for (int pb = 0; pb < 4; ++pb) {
+                        const int r = (lane_t & 31) + 32 * pb;
+                        const _Float16* src = ldst + r * kRowD + 32 * wave + 16 * (lane_t >> 5);
+                        const f16x8 f0 = *reinterpret_cast<const f16x8*>(src), f1 = *reinterpret_cast<const f16x8*>(src + 8);
+                        bool bad = false;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) bad |= !(fabsf((float)f0[i]) <= kF16Safe) || !(fabsf((float)f1[i]) <= kF16Safe);
+                        if (bad) pad_of(r)[0] = 1;
+                    }
+                }
+                amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
+            }
             f32x16 amv[1][2];
             f32x4 biasv[1][4];
             float invv;
             wide_gemm_h<1, 18, 0, kRowD, kPlaneT, true, 2048, 2, 2048, kPeel>(prev, wb, frag128(L.views, 18), xr_h, 0, 0, lane_t, amv);
             load_bias<1>(biasv, invv, wb, (L.views.b + 32 * cg) * 4, (L.views.b + kHalf) * 4, lane_t);
-            prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
+            if constexpr (kMode == kGateHeads) prefetch_w<2>(pre2, wb, frag256(L.as1, 16));
+            else                               prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
             f16x8 hi[2][2], lo[2][2];
             to_operands<1, false, 2, !kSave>(amv, invv, biasv, amax2, hi, lo);
+            if constexpr (kMode == kGateHeads) flag_operands(hi);
             if constexpr (kSave) {                // 128 channels: a four-block fragment slot, block cg of point half ph
                 int lane_o = lane_t;
                 asm volatile("" : "+v"(lane_o));
@@ -417,6 +555,11 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             regop_gemm<2>(wb, (L.resr.w + cg * 2 * 2 * 256) * 4, hi, lo, part_res);
         }
         __syncthreads();                           // feature / dir columns are dead: the exchange area may be written
+        bool my_flagged = false;                   // gated heads: the four flag words of this lane's row (their last writer is behind the barrier; the
+        if constexpr (kMode == kGateHeads) {       // next tile's encode writes them again right behind the next one)
+            const u32x4 f = *reinterpret_cast<const u32x4*>(pad_of(16 * wave + (lane_t & 15)));
+            my_flagged = (f[0] | f[1] | f[2] | f[3]) != 0u;
+        }
         if (lane_t < 32) {
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb) {
@@ -467,7 +610,7 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
         }
         // a wave's 16 points x 11 floats are 704 CONTIGUOUS bytes of raw: they leave as 44 sixteen-byte pieces (lanes 0..43, staged in
         // dead columns of the lo plane), every 64-byte sector written once by one instruction
-        const bool whole_rows = p.channels == INERF_BASE_CHANNELS && tile * kPtsT + kPtsT <= p.n_points &&
+        const bool whole_rows = kMode != kGateHeads && p.channels == INERF_BASE_CHANNELS && tile * kPtsT + kPtsT <= p.n_points &&
                                 (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0;
         auto stage_row = [&](int r) { return reinterpret_cast<float*>(ldst + kPlaneT + r * kRowD + 128); };      // lo plane, bytes 256..299 of row r
         if (lane_t < 16 && my_valid) {
@@ -489,7 +632,16 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             const float sh = sigmoid_ref_h(as4[3]);
             const float r0 = sigmoid_ref_h(res4[0]), r1 = sigmoid_ref_h(res4[1]), r2 = sigmoid_ref_h(res4[2]);
             const float c0 = __fadd_rn(__fmul_rn(a0, sh), r0), c1 = __fadd_rn(__fmul_rn(a1, sh), r1), c2 = __fadd_rn(__fmul_rn(a2, sh), r2);   // run_nerf_helpers.py:320
-            if (whole_rows) {
+            if constexpr (kMode == kGateHeads) {      // the survivor's ten colour channels, to the row of its point; its range flag, to the word of its ray
+                const int pt = p.gate_idx[my_pt];
+                float* const row = p.raw + (size_t)pt * p.channels;
+                __builtin_nontemporal_store(c0, row + 0); __builtin_nontemporal_store(c1, row + 1); __builtin_nontemporal_store(c2, row + 2);
+                __builtin_nontemporal_store(a0, row + 4); __builtin_nontemporal_store(a1, row + 5); __builtin_nontemporal_store(a2, row + 6);
+                __builtin_nontemporal_store(sh, row + 7);
+                __builtin_nontemporal_store(r0, row + 8); __builtin_nontemporal_store(r1, row + 9); __builtin_nontemporal_store(r2, row + 10);
+                if (my_flagged && p.status)
+                    atomicOr(p.status + (p.status_rays > 0 ? (p.ray0 + pt / p.n_samples) / p.status_rays : 0), INERF_STATUS_F16_RANGE);
+            } else if (whole_rows) {
                 float* st = stage_row(16 * wave + lane_t);
                 *reinterpret_cast<f32x4*>(st) = f32x4{c0, c1, c2, sig4[0]};
                 *reinterpret_cast<f32x4*>(st + 4) = f32x4{a0, a1, a2, sh};
@@ -513,7 +665,7 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
             }
             __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.raw + (size_t)(tile * kPtsT + 16 * wave) * INERF_BASE_CHANNELS) + lane_t);
         }
-        flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
+        if constexpr (kMode != kGateHeads) flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
         // (the next tile's encode writes bytes 0..127 and 512..575 of the rows, both planes: clear of the exchange area (hi plane, bytes
         // 128..255) and of the staging rows (lo plane, bytes 256..299) this tile's last readers may still be in)
     }
@@ -523,6 +675,86 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (lane == 0 && m == m) atomicMax(reinterpret_cast<unsigned int*>(p.act_max), __builtin_bit_cast(unsigned int, m));
     }
+}
+
+template <bool kSsr, bool kSave = false, bool kPipe = false>
+__global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParams p) {
+    encode_mlp_t128_tiles<kSsr, kSave, kPipe, kWhole>(p);
+}
+__global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk>(p); }
+__global__ __launch_bounds__(512, 2) void k_mlp_gate_heads_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateHeads>(p); }
+
+// ---- the density gate's launcher ----
+// A launch is walked in sub-ranges of whole rays, each as trunk kernel then heads kernel on the same stream.  The record buffer holds one
+// record per POINT of a sub-range - every point surviving is the worst case - so it cannot overflow.  Its size comes from a byte budget:
+// INERF_GATE_BYTES, default 2 GiB = 2 M points = 64 tiles per CU per trunk launch (DESIGN.md 3.1c on the tail that implies).
+static int64_t gate_budget_points() {
+    int64_t bytes = (int64_t)2 << 30;
+    if (const char* e = getenv("INERF_GATE_BYTES")) {
+        const double v = atof(e);
+        if (v >= 1.0) bytes = v < 6.0e10 ? (int64_t)v : (int64_t)6.0e10;
+    }
+    return bytes / (kGateRecordBytes + 4);
+}
+
+bool mlp_gate_applies(const inerf_net_desc& net, uint32_t flags) {
+    return net.precision == INERF_PREC_F16X3 && net.variant == INERF_VARIANT_OBJECT && !(flags & INERF_FLAG_ENDPOINT) && !getenv("INERF_F16_KERNEL");
+}
+
+GatePlan mlp_gate_plan(int64_t n_rays, int n_samples) {
+    GatePlan g{};
+    if (n_rays <= 0 || n_samples < 1) return g;
+    const int64_t fit = gate_budget_points() / n_samples;
+    g.rays_per_sub = fit < 1 ? 1 : fit < n_rays ? fit : n_rays;
+    g.n_sub = (n_rays + g.rays_per_sub - 1) / g.rays_per_sub;
+    const int64_t pts = g.rays_per_sub * n_samples;
+    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    g.idx_off = up(pts * kGateRecordBytes);
+    g.count_off = g.idx_off + up(pts * 4);
+    g.bytes = g.count_off + up(g.n_sub * 4);
+    return g;
+}
+
+int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, hipStream_t stream) {
+    const GatePlan g = mlp_gate_plan(n_rays, p0.n_samples);
+    char* const ws = static_cast<char*>(gate_ws);
+    unsigned int* const counts = reinterpret_cast<unsigned int*>(ws + g.count_off);
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)g.n_sub * 4, stream);
+    if (e != hipSuccess) return record(e);
+    static PerDeviceOnce attr_set;
+    if (attr_set.first()) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_heads_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
+        if (e != hipSuccess) return record(e);
+        attr_set.mark();
+    }
+    for (int64_t s = 0; s < g.n_sub; ++s) {
+        const int64_t r0 = s * g.rays_per_sub, nr = n_rays - r0 < g.rays_per_sub ? n_rays - r0 : g.rays_per_sub;
+        MlpParams p = p0;
+        p.rays += r0 * INERF_RAY_FLOATS;
+        p.z += r0 * p0.n_samples;
+        p.raw += r0 * p0.n_samples * p0.channels;
+        p.ray0 = (int)r0;
+        p.n_points = (int)(nr * p0.n_samples);
+        p.n_tiles = (p.n_points + kPtsT - 1) / kPtsT;
+        p.gate_rec = reinterpret_cast<unsigned char*>(ws);
+        p.gate_idx = reinterpret_cast<int*>(ws + g.idx_off);
+        p.gate_count = counts + s;
+        const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
+        hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);
+        hipLaunchKernelGGL(k_mlp_gate_heads_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);      // (persistent: its tile count is on the device)
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess && getenv("INERF_GATE_LOG")) {      // debug: the survivor share of this launch (synchronises - not for timed runs)
+        std::vector<unsigned int> h((size_t)g.n_sub);
+        e = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = hipMemcpy(h.data(), counts, h.size() * 4, hipMemcpyDeviceToHost);
+        unsigned long long kept = 0;
+        for (unsigned int c : h) kept += c;
+        fprintf(stderr, "inerf gate: %lld rays x %d samples in %lld sub-launches, %llu of %lld points survive (%.4f)\n", (long long)n_rays,
+                p0.n_samples, (long long)g.n_sub, kept, (long long)(n_rays * p0.n_samples), (double)kept / (double)(n_rays * p0.n_samples));
+    }
+    return record(e);
 }
 
 int launch_mlp_f16x3_t128(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream) {

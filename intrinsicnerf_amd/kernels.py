@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _capi
-from ._capi import (BASE_CHANNELS, ENDPOINT_DIM, FLAG_ENDPOINT, FLAG_LINDISP, FLAG_U_PER_RAY, FLAG_WHITE_BKGD,
+from ._capi import (BASE_CHANNELS, ENDPOINT_DIM, FLAG_ENDPOINT, FLAG_GATE_COLOUR, FLAG_LINDISP, FLAG_U_PER_RAY, FLAG_WHITE_BKGD,
                     RAY_FLOATS, CompositeOut, RenderArgs)
 
 MAX_POINTS_PER_LAUNCH = (1 << 31) - 1
@@ -224,6 +224,11 @@ def coalesced_chunk(n_rays, chunk, n_samples, n_importance, channels, device):
         return chunk
     if device.type == "cuda":
         cap = min(cap, torch.cuda.mem_get_info(device)[0] // 2)
+    # the density gate's record buffer (include/inerf.h INERF_FLAG_GATE_COLOUR: at most INERF_GATE_BYTES, default 2 GiB) is a fixed part
+    # of a large launch's workspace, whatever the ray count; a cap below twice that budget is taken as it is (the buffer comes on top)
+    gate = int(float(os.environ.get("INERF_GATE_BYTES", 2 * 2 ** 30)))
+    if os.environ.get("INERF_GATE", "1")[:1] != "0" and cap >= 2 * gate:
+        cap -= gate
     s, f = int(n_samples), int(n_samples) + int(n_importance)
     # per ray: z coarse / new / merged, coarse weights, raw of both levels, maps (include/inerf.h: inerf_render_workspace_bytes), + 10 %
     per_ray = int(1.1 * 4 * (s + n_importance + f + s + (s + f) * channels + 2 * (16 + channels)))
@@ -258,15 +263,16 @@ def with_f32_fallback(desc, run):
         return run(d32)
 
 
-def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None):
+def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_colour=False, status_rays=0):
     """raw[N,S,CH]: fused encoding + MLP (run_network + NeRF.forward).
 
-    ``status``: optional int32[1] device tensor that collects INERF_STATUS_* bits (PREC_F16X3 range check)."""
+    ``status``: optional int32[1] device tensor that collects INERF_STATUS_* bits (PREC_F16X3 range check); with ``status_rays`` > 0
+    one word per that many rays.  ``gate_colour``: INERF_FLAG_GATE_COLOUR (include/inerf.h) - rows with sigma <= 0 carry zero colours."""
     rays = _dev(rays, "rays", (None, RAY_FLOATS))
     z_vals = _dev(z_vals, "z_vals", (rays.shape[0], None))
     packed = _dev(packed, "packed weights", (None,))
     n, s = z_vals.shape
-    flags = FLAG_ENDPOINT if endpoint else 0
+    flags = (FLAG_ENDPOINT if endpoint else 0) | (FLAG_GATE_COLOUR if gate_colour else 0)
     ch = _capi.lib().inerf_raw_channels(desc, flags, 1)
     raw = _new(rays, n, s, ch)
     with torch.cuda.device(rays.device):
@@ -274,10 +280,10 @@ def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None):
         if ws_bytes < 0:
             _capi.check(ws_bytes, "inerf_encode_mlp_workspace_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=rays.device) if ws_bytes > 0 else None
-        rc = _capi.lib().inerf_encode_mlp_ws(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
-                                             None if status is None else C.c_void_p(status.data_ptr()),
-                                             None if ws is None else C.c_void_p(ws.data_ptr()), ws_bytes, _stream(rays))
-    _capi.check(rc, "inerf_encode_mlp_ws")
+        rc = _capi.lib().inerf_encode_mlp_chunked(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
+                                                  None if status is None else C.c_void_p(status.data_ptr()), int(status_rays),
+                                                  None if ws is None else C.c_void_p(ws.data_ptr()), ws_bytes, _stream(rays))
+    _capi.check(rc, "inerf_encode_mlp_chunked")
     return raw
 
 
