@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40012
+#define INERF_ABI_VERSION 40013
 
 /* error codes */
 #define INERF_OK              0
@@ -666,6 +666,105 @@ typedef struct inerf_adam_args {
     double eps;
 } inerf_adam_args;
 int inerf_adam_step(const inerf_adam_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training batch assembly: from a pixel draw to the finished batch, one thread per selected pixel.
+ * Replaces the first part of an iteration of both trainers: object_level/run_nerf.py:886-938 (img_i, get_rays, the coords
+ * meshgrid, np.random.choice(replace=False), select_neighbor and the gathers that give batch_rays / target_s / target_m) and
+ * SSR/training/trainer.py:627-691 with no_batching=True (sampling_index, rays.py:153-172, and the gathers that give
+ * sampled_rays / gt_rgb / gt_depth / gt_semantic).  The 2n output rows are the n selected pixels followed by their n neighbours.
+ *
+ * Pixels.  INERF_BATCH_OBJECT: pixel q of the window [row0, row0 + win_h) x [col0, col0 + win_w) (the whole frame, or the centre
+ *   crop H/2 +- dH, W/2 +- dW of run_nerf.py:902-909, computed by the caller) is (row0 + q / win_w, col0 + q % win_w).
+ *   INERF_BATCH_SSR: q is the flat pixel h * width + w of the frame (the window fields are ignored).
+ *   Neighbour: (row + off_row, col + off_col), each clamped to the IMAGE ([0, height-1], [0, width-1]), never to the window.
+ * Rays.  OBJECT: out_rays is [2, 2n, 3], origins then directions, computed from poses[image] with k_gen_rays' operation order
+ *   (bit-identical to get_rays followed by the reference's gather; no whole-frame table is built).  SSR: out_rays is [2n, 11]:
+ *   rows of ray_table [n_images, H*W, 11] when it is non-NULL, else the rows inerf_gen_rays writes for poses / fx..far.
+ *   INERF_BATCH_OPENGL selects the camera convention of computed rays (INERF_CAM_OPENGL; the object level always sets it).
+ * Tables (all device-resident, contiguous):
+ *   images [n_images, H, W, 3], image_bytes 4 (fp32) or 8 (fp64; SSR only - the SSR trainers hold fp64 images and depths);
+ *     out_rgb [2n, 3] has the same element type.
+ *   aux: OBJECT masks [n_images, H, W, 1] fp32 -> out_aux [2n, 1]; SSR depth [n_images, H, W], aux_bytes 4 or 8 -> out_aux [2n].
+ *     Optional (NULL: not gathered).
+ *   semantic (SSR, optional) [n_images, H, W], semantic_bytes 1 (uint8), 2, 4 or 8 (signed) -> out_semantic [2n] int64.
+ *   avail (SSR, optional) [n_images] fp64 (the trainer's mask_ids) -> out_avail [1] = avail[image].
+ * Indices, form (a) (INERF_BATCH_DRAW clear): image_index (DEVICE, one int64; NULL: the host value image_host), pixels [n]
+ *   int64 (q as above), off_row / off_col [n] int64 with values in {-1, 0, 1}.  The library never reads device memory on the
+ *   host: a device index outside its table is clamped into it (an offset into [-1, 1]) and INERF_BATCH_STATUS_INDEX is raised.
+ * Indices, form (b) (INERF_BATCH_DRAW): drawn in the kernel from (seed, step, ray) by 32-bit integer hashing (no floating point:
+ *   tests/_batch_draw.py restates it bit for bit; DESIGN.md section 3, "Training batches").  step is the host value, or *step_dev (one int64) when that is
+ *   non-NULL; INERF_BATCH_ADVANCE adds 1 to *step_dev in a second one-thread launch after the batch, so a replayed graph draws a
+ *   new batch each time.  Image: hash -> image_ids[j] (DEVICE int64 [n_image_ids]; NULL: j itself, over n_images).  Offsets:
+ *   hash -> {-1, 0, 1}.  OBJECT pixels are DISTINCT within a step (np.random.choice(replace=False)): ray k takes perm(k) of a keyed
+ *   Feistel bijection on the smallest power-of-two domain covering M = win_h * win_w, cycle-walked back into [0, M).  The walk is
+ *   bounded by INERF_BATCH_MAX_WALK; at the bound the value is taken modulo M (a possible duplicate, never a hang) and
+ *   INERF_BATCH_STATUS_WALK is raised.  SSR pixels are drawn with replacement (hash mod H*W, as torch.randint).
+ *   out_image [1], out_pixels [n], out_off_row [n], out_off_col [n] (int64, optional) receive the indices used, in either form.
+ * status: optional device int32 word, OR-ed into (the caller zeroes it).
+ * n == 0 is a no-op (INERF_OK, nothing launched, *step_dev untouched).  Returns INERF_E_INVALID for a null required pointer, n < 0,
+ * a window that leaves the image, image_host outside [0, n_images), an element size not listed above, n > M in the distinct
+ * draw, or INERF_BATCH_ADVANCE without step_dev; INERF_E_UNSUPPORTED for H * W or n beyond 2^31 - 1.  Nothing is allocated,
+ * synchronised or read on the host; capturable into a HIP graph.  No atomics except the OR into `status`; bit-identical from run
+ * to run and between a direct launch and a replayed one. */
+#define INERF_BATCH_OBJECT 0
+#define INERF_BATCH_SSR    1
+#define INERF_BATCH_DRAW     1u
+#define INERF_BATCH_ADVANCE  2u
+#define INERF_BATCH_OPENGL   4u
+#define INERF_BATCH_STATUS_WALK   1
+#define INERF_BATCH_STATUS_INDEX  2
+#define INERF_BATCH_MAX_WALK 64
+typedef struct inerf_batch_args {
+    int32_t form;
+    uint32_t flags;
+    int64_t n;
+    int32_t n_images;
+    int32_t height;
+    int32_t width;
+    int32_t row0;
+    int32_t col0;
+    int32_t win_h;
+    int32_t win_w;
+    int32_t pose_stride;
+    const float* poses;
+    float fx;
+    float fy;
+    float cx;
+    float cy;
+    float near;
+    float far;
+    const float* ray_table;
+    const void* images;
+    const void* aux;
+    const void* semantic;
+    const double* avail;
+    int32_t image_bytes;
+    int32_t aux_bytes;
+    int32_t semantic_bytes;
+    int32_t image_host;
+    const int64_t* image_index;
+    const int64_t* pixels;
+    const int64_t* off_row;
+    const int64_t* off_col;
+    uint64_t seed;
+    int64_t step;
+    int64_t* step_dev;
+    const int64_t* image_ids;
+    int32_t n_image_ids;
+    int32_t reserved;
+    float* out_rays;
+    void* out_rgb;
+    void* out_aux;
+    int64_t* out_semantic;
+    double* out_avail;
+    int64_t* out_image;
+    int64_t* out_pixels;
+    int64_t* out_off_row;
+    int64_t* out_off_col;
+    int32_t* status;
+} inerf_batch_args;
+int inerf_batch_assemble(const inerf_batch_args* args, void* stream);
 
 #ifdef __cplusplus
 }

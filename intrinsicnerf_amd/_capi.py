@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40012          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40013          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -85,6 +85,25 @@ class AdamArgs(C.Structure):
                 ("lr_dev", C.c_void_p), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
+class BatchArgs(C.Structure):
+    _fields_ = [("form", C.c_int32), ("flags", C.c_uint32), ("n", C.c_int64), ("n_images", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32),
+                ("pose_stride", C.c_int32), ("poses", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("near", C.c_float), ("far", C.c_float), ("ray_table", C.c_void_p), ("images", C.c_void_p),
+                ("aux", C.c_void_p), ("semantic", C.c_void_p), ("avail", C.c_void_p), ("image_bytes", C.c_int32),
+                ("aux_bytes", C.c_int32), ("semantic_bytes", C.c_int32), ("image_host", C.c_int32), ("image_index", C.c_void_p),
+                ("pixels", C.c_void_p), ("off_row", C.c_void_p), ("off_col", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_int64),
+                ("step_dev", C.c_void_p), ("image_ids", C.c_void_p), ("n_image_ids", C.c_int32), ("reserved", C.c_int32),
+                ("out_rays", C.c_void_p), ("out_rgb", C.c_void_p), ("out_aux", C.c_void_p), ("out_semantic", C.c_void_p),
+                ("out_avail", C.c_void_p), ("out_image", C.c_void_p), ("out_pixels", C.c_void_p), ("out_off_row", C.c_void_p),
+                ("out_off_col", C.c_void_p), ("status", C.c_void_p)]
+
+
+BATCH_OBJECT, BATCH_SSR = 0, 1
+BATCH_DRAW, BATCH_ADVANCE, BATCH_OPENGL = 1, 2, 4
+BATCH_STATUS_WALK, BATCH_STATUS_INDEX = 1, 2
+BATCH_MAX_WALK = 64
+
 ADAM_TABLE_TENSORS = 72      # tensors per launch of inerf_adam_step (its by-value kernel-argument table)
 
 LOSS_KEY_LABELS, LOSS_MASK_OUTER = 1, 2
@@ -155,6 +174,7 @@ SYMBOLS = {
     "inerf_intrinsic_loss": (_I, [C.POINTER(LossArgs), _P]),
     "inerf_intrinsic_loss_backward": (_I, [C.POINTER(LossArgs), _P]),
     "inerf_adam_step": (_I, [C.POINTER(AdamArgs), _P]),
+    "inerf_batch_assemble": (_I, [C.POINTER(BatchArgs), _P]),
 }
 
 _lib = None

@@ -959,3 +959,183 @@ def mlp_train(desc, module, rays, z_vals, endpoint=False):
         return _FusedMlpFn.apply(rays, z_vals, d, bool(endpoint), names, exact, *params)
     return torch.cat([_FusedMlpFn.apply(rays[i:i + per], z_vals[i:i + per], d, bool(endpoint), names, exact, *params)
                       for i in range(0, n, per)], 0)
+
+
+# ---------------------------------------------------------------- training batch assembly (csrc/batch.hip)
+_INDEX_NAMES = ("image", "pixels", "off_row", "off_col")
+
+
+def _table(t, name, dtypes, shape, like=None):
+    """A device-resident table of one of ``dtypes`` with ``shape`` (None: any extent), contiguous."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} lives on {t.device}: intrinsicnerf_amd runs only on a HIP device "
+                           "(no CPU / eager fallback exists)")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name} must be one of {[str(d) for d in dtypes]}, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and int(t.shape[i]) != s for i, s in enumerate(shape)):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple('*' if s is None else s for s in shape)}")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name} is on {t.device}, expected {like.device}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _batch_indices(a, n, indices, draw, like):
+    """Fill the index half of a BatchArgs: form (a) from ``indices`` = (image, pixels, off_row, off_col), form (b) from
+    ``draw`` = dict(seed, step | step_dev, advance, image_ids).  Returns the tensors whose pointers it stored: a ``.contiguous()``
+    copy among them must stay referenced until the launch is issued (its block could otherwise be handed to an output)."""
+    keep = []
+    if (indices is None) == (draw is None):
+        raise ValueError("give either indices=(image, pixels, off_row, off_col) or draw=dict(seed=..., step=...)")
+    if indices is not None:
+        image, pixels, off_row, off_col = indices
+        if isinstance(image, torch.Tensor):
+            image = _table(image.reshape(-1), "indices[0] (image)", (torch.int64,), (1,), like)
+            a.image_index = _ptr(image)
+            keep.append(image)
+        else:
+            a.image_host = int(image)
+        for name, t in (("pixels", pixels), ("off_row", off_row), ("off_col", off_col)):
+            t = _table(t, f"indices ({name})", (torch.int64,), (n,), like)
+            setattr(a, name, _ptr(t))
+            keep.append(t)
+        return keep
+    a.flags |= _capi.BATCH_DRAW
+    a.seed = int(draw["seed"]) & 0xFFFFFFFFFFFFFFFF
+    step_dev = draw.get("step_dev")
+    if step_dev is not None:
+        step_dev = _table(step_dev, "step_dev", (torch.int64,), (1,), like)
+        a.step_dev = _ptr(step_dev)
+        keep.append(step_dev)
+        if draw.get("advance", False):
+            a.flags |= _capi.BATCH_ADVANCE
+    else:
+        a.step = int(draw.get("step", 0))
+    ids = draw.get("image_ids")
+    if ids is not None:
+        ids = _table(ids, "image_ids", (torch.int64,), (None,), like)
+        a.image_ids, a.n_image_ids = _ptr(ids), ids.shape[0]
+        keep.append(ids)
+    return keep
+
+
+def _batch_index_outputs(a, n, like, want):
+    if not want:
+        return None
+    out = {"image": torch.empty(1, dtype=torch.int64, device=like.device)}
+    out.update({k: torch.empty(n, dtype=torch.int64, device=like.device) for k in _INDEX_NAMES[1:]})
+    a.out_image, a.out_pixels, a.out_off_row, a.out_off_col = (_ptr(out[k]) for k in _INDEX_NAMES)
+    return out
+
+
+def _batch_poses(poses, like=None):
+    poses = _dev(poses, "poses")
+    if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+        raise ValueError(f"poses has shape {tuple(poses.shape)}, expected [n_images, 3|4, 4]")
+    if like is not None and poses.device != like.device:
+        raise ValueError(f"poses is on {poses.device}, expected {like.device}")
+    return poses
+
+
+def check_batch_status(status, what="inerf_batch_assemble"):
+    """Raise if a batch launch clamped a supplied index or ran into the bound of its cycle walk (reads the word: synchronises)."""
+    word = int(status.item())
+    if word & _capi.BATCH_STATUS_INDEX:
+        raise IndexError(f"{what}: an index lies outside its table (it was clamped into it)")
+    if word & _capi.BATCH_STATUS_WALK:
+        raise RuntimeError(f"{what}: the cycle walk of the pixel permutation reached its bound of {_capi.BATCH_MAX_WALK} (duplicate pixel)")
+
+
+def batch_object(images, masks, poses, intrinsics, window, n, indices=None, draw=None, status=None, return_indices=False):
+    """Object-level training batch (run_nerf.py:886-938) through ``inerf_batch_assemble``: ``(batch_rays [2, 2n, 3],
+    target_s [2n, 3], target_m [2n, 1] | None)`` - the n selected pixels, then their n neighbours - plus the dict of the indices
+    used with ``return_indices``.  ``images`` [n_img, H, W, 3] / ``masks`` [n_img, H, W, 1] | None / ``poses`` [n_img, 3|4, 4]:
+    fp32, device-resident.  ``intrinsics`` = (fx, fy, cx, cy); ``window`` = (row0, col0, rows, cols).  ``indices`` =
+    (image, pixels, off_row, off_col) (form a) or ``draw`` = dict(seed, step | step_dev [, advance, image_ids]) (form b)."""
+    images = _dev(images, "images", (None, None, None, 3))
+    n_img, h, w = (int(s) for s in images.shape[:3])
+    masks = _opt(masks, "masks", (n_img, h, w, 1), images)
+    poses = _batch_poses(poses, images)
+    if poses.shape[0] != n_img:
+        raise ValueError(f"{poses.shape[0]} poses for {n_img} images")
+    n = int(n)
+    a = _capi.BatchArgs()
+    a.form, a.flags, a.n = _capi.BATCH_OBJECT, _capi.BATCH_OPENGL, n
+    a.n_images, a.height, a.width = n_img, h, w
+    a.row0, a.col0, a.win_h, a.win_w = (int(v) for v in window)
+    a.poses, a.pose_stride = _ptr(poses), poses.shape[1] * 4
+    a.fx, a.fy, a.cx, a.cy = (float(v) for v in intrinsics)
+    a.images, a.image_bytes = _ptr(images), 4
+    held = _batch_indices(a, n, indices, draw, images) if n >= 0 else None
+    rays, target_s = _new(images, 2, 2 * max(n, 0), 3), _new(images, 2 * max(n, 0), 3)
+    target_m = _new(images, 2 * max(n, 0), 1) if masks is not None else None
+    a.out_rays, a.out_rgb = _ptr(rays), _ptr(target_s)
+    if masks is not None:
+        a.aux, a.aux_bytes, a.out_aux = _ptr(masks), 4, _ptr(target_m)
+    a.status = _ptr(status)
+    idx = _batch_index_outputs(a, max(n, 0), images, return_indices)
+    with torch.cuda.device(images.device):
+        rc = _capi.lib().inerf_batch_assemble(C.byref(a), _stream(images))
+    del held                                  # (referenced until the launch was issued; the stream orders the rest)
+    _capi.check(rc, "inerf_batch_assemble")
+    return (rays, target_s, target_m, idx) if return_indices else (rays, target_s, target_m)
+
+
+_SEMANTIC_DTYPES = (torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def batch_ssr(image, depth, semantic, n, rays=None, camera=None, avail=None, indices=None, draw=None, status=None,
+              return_indices=False):
+    """SSR training batch (trainer.py:627-691 with no_batching=True; sampling_index, rays.py:153-172) through
+    ``inerf_batch_assemble``: ``(sampled_rays [2n, 11], gt_rgb [2n, 3], gt_depth [2n] | None, gt_semantic [2n] int64 | None,
+    avail [1] fp64 | None)`` (+ the indices dict).  ``image`` [n_img, H, W, 3] fp32 | fp64, ``depth`` [n_img, H, W] fp32 | fp64,
+    ``semantic`` [n_img, H, W] uint8 | int16 | int32 | int64, ``avail`` [n_img] fp64 (mask_ids): device-resident.  Rays: rows of
+    ``rays`` [n_img, H*W, 11], or computed from ``camera`` = dict(poses, fx, fy, cx, cy, near, far, opengl) as inerf_gen_rays
+    writes them.  ``indices`` / ``draw`` as in ``batch_object`` (pixels are flat h * W + w; drawn ones come with replacement)."""
+    image = _table(image, "image", (torch.float32, torch.float64), (None, None, None, 3))
+    n_img, h, w = (int(s) for s in image.shape[:3])
+    n = int(n)
+    a = _capi.BatchArgs()
+    a.form, a.n = _capi.BATCH_SSR, n
+    a.n_images, a.height, a.width = n_img, h, w
+    a.images, a.image_bytes = _ptr(image), image.element_size()
+    if (rays is None) == (camera is None):
+        raise ValueError("give either the ray table `rays` or `camera`")
+    if rays is not None:
+        rays = _table(rays, "rays", (torch.float32,), (n_img, h * w, RAY_FLOATS), image)
+        a.ray_table = _ptr(rays)
+    else:
+        poses = _batch_poses(camera["poses"], image)
+        if poses.shape[0] != n_img:
+            raise ValueError(f"{poses.shape[0]} poses for {n_img} images")
+        a.poses, a.pose_stride = _ptr(poses), poses.shape[1] * 4
+        a.fx, a.fy, a.cx, a.cy, a.near, a.far = (float(camera[k]) for k in ("fx", "fy", "cx", "cy", "near", "far"))
+        if camera.get("opengl", False):
+            a.flags |= _capi.BATCH_OPENGL
+    rows = 2 * max(n, 0)
+    out_rays = _new(image, rows, RAY_FLOATS)
+    out_rgb = torch.empty((rows, 3), dtype=image.dtype, device=image.device)
+    a.out_rays, a.out_rgb = _ptr(out_rays), _ptr(out_rgb)
+    out_depth = out_sem = out_avail = None
+    if depth is not None:
+        depth = _table(depth, "depth", (torch.float32, torch.float64), (n_img, h, w), image)
+        out_depth = torch.empty(rows, dtype=depth.dtype, device=image.device)
+        a.aux, a.aux_bytes, a.out_aux = _ptr(depth), depth.element_size(), _ptr(out_depth)
+    if semantic is not None:
+        semantic = _table(semantic, "semantic", _SEMANTIC_DTYPES, (n_img, h, w), image)
+        out_sem = torch.empty(rows, dtype=torch.int64, device=image.device)
+        a.semantic, a.semantic_bytes, a.out_semantic = _ptr(semantic), semantic.element_size(), _ptr(out_sem)
+    if avail is not None:
+        avail = _table(avail, "avail", (torch.float64,), (n_img,), image)
+        out_avail = torch.zeros(1, dtype=torch.float64, device=image.device) if n <= 0 else torch.empty(1, dtype=torch.float64, device=image.device)
+        a.avail, a.out_avail = _ptr(avail), _ptr(out_avail)
+    held = _batch_indices(a, n, indices, draw, image) if n >= 0 else None
+    a.status = _ptr(status)
+    idx = _batch_index_outputs(a, max(n, 0), image, return_indices)
+    with torch.cuda.device(image.device):
+        rc = _capi.lib().inerf_batch_assemble(C.byref(a), _stream(image))
+    del held
+    _capi.check(rc, "inerf_batch_assemble")
+    out = (out_rays, out_rgb, out_depth, out_sem, out_avail)
+    return out + (idx,) if return_indices else out

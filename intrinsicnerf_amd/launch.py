@@ -36,6 +36,12 @@ by ``optim.Adam`` (csrc/adam.hip: one launch of the library per step) over the s
 ``SSRTrainer.create_ssr`` (it assigns ``self.optimizer``, trainer.py:848).  Nothing in ``torch.optim`` is patched; the
 trainers' ``optimizer.zero_grad()``, ``optimizer.step()``, learning-rate decay and ``optimizer.state_dict()`` stay their lines.
 
+``--inerf-batches`` (opt-in) assembles the SSR training batch in one launch of csrc/batch.hip: ``SSRTrainer.sample_data``
+(trainer.py:627-691) becomes ``ssr.SSRRenderMixin.sample_data`` - the draws stay the reference's own ``sampling_index``
+(rays.py:153-172), so a seeded run selects the reference's pixels; every gather is the one launch.  The object-level batch code
+is inline in ``train()`` (run_nerf.py:886-938) and cannot be rebound from outside: for ``run_nerf.py`` the flag only says so, once;
+INTEGRATION.md has its three-line replacement by ``batches.ObjectBatcher.next(i)``.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -142,7 +148,7 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     bound = {}
@@ -178,10 +184,25 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
         bound.setdefault("SSR.training.trainer", []).append(LOSS_SYMBOL)
     if adam:                                           # (create_ssr is the mixin's by now: the wrapper goes around that one)
         trainer.SSRTrainer.create_ssr = _with_inerf_adam_ssr(trainer.SSRTrainer.create_ssr)
+    if batches:                                        # trainer.py:627-691; its draws stay SSR.models.rays.sampling_index
+        trainer.SSRTrainer.sample_data = ssr.SSRRenderMixin.sample_data
+        bound["SSR.training.trainer.SSRTrainer"].append("sample_data")
     return bound
 
 
-def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False):
+_told_object_batches = False
+
+
+def _object_batches_notice():
+    """Said once: run_nerf.py builds its batch inline in train() (run_nerf.py:886-938); nothing there can be rebound."""
+    global _told_object_batches
+    if not _told_object_batches:
+        print("intrinsicnerf_amd.launch: --inerf-batches has no effect on run_nerf.py: its batch code is inline in train() "
+              "(run_nerf.py:886-938).  Replace those lines by batches.ObjectBatcher.next(i) (INTEGRATION.md).", file=sys.stderr)
+        _told_object_batches = True
+
+
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -196,9 +217,11 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     exec(body, mod.__dict__)
     if kind == "object":
         mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam)
+        if batches:
+            _object_batches_notice()
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches)
     return mod, main
 
 
@@ -216,6 +239,9 @@ def main(argv=None):
     adam = "--inerf-adam" in argv
     if adam:
         argv.remove("--inerf-adam")
+    batches = "--inerf-batches" in argv
+    if batches:
+        argv.remove("--inerf-batches")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -223,8 +249,11 @@ def main(argv=None):
     from . import _capi
     _capi.lib()                                        # fail now, and loudly, if the HIP library is missing
     # (positional as before for the first two; the loss flag only when given, so a two-flag `prepare` stand-in keeps working)
-    if adam:                                           # (by keyword and only when given, for the same reason)
-        mod, main_code = prepare(script, with_render_path, cluster_fit, losses, adam=True)
+    extra = dict(adam=True) if adam else {}            # (by keyword and only when given, for the same reason)
+    if batches:
+        extra["batches"] = True
+    if extra:
+        mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses) if losses else prepare(script, with_render_path, cluster_fit)
     sys.argv = [script] + argv[1:]                     # the script's own argument parser sees its own command line

@@ -11,6 +11,7 @@ Mirrors, with identical names / argument meaning / returned keys (citations rela
 ``SSRTrainer`` keeps its data loading, losses and logging; it only has to inherit the mixin (or
 assign the three methods) - see INTEGRATION.md.  All arithmetic runs in ``libinerf.so``.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -550,6 +551,64 @@ class SSRRenderMixin:
             o.update({k + "_fine": v for k, v in f.items()})
             o["raw_fine"], o["z_std"] = raw, z_std
         return o
+
+    def sample_data(self, step, rays, h, w, no_batching=True, mode="train"):
+        """``SSRTrainer.sample_data`` (trainer.py:627-691).  With ``no_batching`` the draws are the reference's own
+        ``sampling_index`` (a seeded run selects the reference's pixels) and every gather is ONE launch of
+        ``inerf_batch_assemble``; returns the reference's 5-tuple (2-tuple without ``enable_semantic``), the availability flag
+        being ``mask_ids[index_batch]`` as the reference forms it.  ``no_batching=False`` keeps the reference's torch lines.
+        A holder that is not the reference's trainer may carry its own draw function as the INSTANCE attribute ``sampling_index``
+        (same signature; set on a class it would have to be a ``staticmethod``)."""
+        num_img, num_ray, ray_dim = rays.shape
+        assert num_ray == h * w
+        total_ray_num = num_img * h * w
+        if mode == "train":
+            image, sample_num = self.train_image, self.num_train
+            depth, semantic = (self.train_depth, self.train_semantic) if self.enable_semantic else (None, None)
+        elif mode == "test":
+            image, sample_num = self.test_image, self.num_test
+            depth, semantic = (self.test_depth, self.test_semantic) if self.enable_semantic else (None, None)
+        else:
+            assert False
+        sematic_available_flag = 1
+        if no_batching:
+            draw = getattr(self, "sampling_index", None)
+            if draw is None:
+                import sys
+                mod = sys.modules.get("SSR.models.rays")
+                if mod is None:
+                    raise RuntimeError("sample_data draws with the reference's sampling_index: import SSR.models.rays (the launcher "
+                                       "does) or set `sampling_index` on the trainer")
+                draw = mod.sampling_index
+            index_batch, index_hw = draw(self.n_rays, num_img, h, w)
+            # [1, 2n]: the n drawn pixels, then their clamped neighbours.  The kernel takes the pixel and the two offsets and clamps
+            # itself; after the clamp the offsets are what is left of the reference's bias_h / bias_w, so the rows are the same.
+            n = index_hw.shape[1] // 2
+            sel, nei = index_hw[0, :n], index_hw[0, n:]
+            packed = torch.stack([sel, torch.div(nei, w, rounding_mode="floor") - torch.div(sel, w, rounding_mode="floor"),
+                                  nei % w - sel % w]).to(device=rays.device, dtype=torch.int64)          # one upload
+            image_index = int(np.asarray(index_batch).reshape(-1)[0])
+            out = kernels.batch_ssr(image.reshape(sample_num, h, w, 3), None if depth is None else depth.reshape(sample_num, h, w),
+                                    None if semantic is None else semantic.reshape(sample_num, h, w), n, rays=rays,
+                                    indices=(image_index, packed[0], packed[1], packed[2]))
+            flat_sampled_rays, gt_image, gt_depth, gt_semantic = out[:4]
+            if self.enable_semantic:
+                sematic_available_flag = self.mask_ids[index_batch]
+        else:
+            index_hw = self.rand_idx[self.i_batch:self.i_batch + self.n_rays]
+            flat_sampled_rays = rays.reshape([-1, ray_dim]).float()[index_hw, :]
+            gt_image = image.reshape(-1, 3)[index_hw, :]
+            if self.enable_semantic:
+                gt_depth = depth.reshape(-1)[index_hw]
+                gt_semantic = semantic.reshape(-1)[index_hw].cuda()
+            self.i_batch += self.n_rays
+            if self.i_batch >= total_ray_num:
+                print("Shuffle data after an epoch!")
+                self.rand_idx = torch.randperm(total_ray_num)
+                self.i_batch = 0
+        if self.enable_semantic:
+            return flat_sampled_rays, gt_image, gt_depth, gt_semantic.long(), sematic_available_flag
+        return flat_sampled_rays, gt_image
 
     def create_ssr(self):
         """Build coarse + fine Semantic_NeRF and the encoders - trainer.py:811-846 (optimiser included)."""

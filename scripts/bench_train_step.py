@@ -2,12 +2,15 @@
 """Training-step timing through the object-level front-end (staged path: HIP sampling / compositing with HIP backward,
 network layers through torch autograd) and the compositing kernels' HBM rates.
 
-    python scripts/bench_train_step.py [--rays 2048] [--iters 10] [--ssr C] [--loss intrinsic] [--optimizer inerf]
+    python scripts/bench_train_step.py [--rays 2048] [--iters 10] [--ssr C] [--loss intrinsic] [--optimizer inerf] [--batch inerf]
 ``--loss intrinsic`` times the step with the loss the reference trains with (compute_intrinsic_loss on both levels, image and
 cluster MSE, the SSR cross-entropy) instead of the default stand-in loss - once as torch expressions (scripts/torch_losses.py)
 and once on the two launches of csrc/losses.hip, alternating in the same process.
 ``--optimizer inerf`` (with ``--loss intrinsic``) adds a third step to that alternation: the HIP loss with ``optim.Adam``
 (csrc/adam.hip) in place of torch.optim.Adam over the same parameters - the step next to it is its parent figure on the same box.
+``--batch inerf`` times the whole object-level step with its batch assembled per iteration - once by the trainer's host + torch
+expressions (scripts/torch_batches.py: image upload, whole-frame rays, host permutation, gathers) and once by
+``batches.ObjectBatcher.next()`` (csrc/batch.hip) - alternating in the same process; 100 images of 400 x 400 (``--frame``).
 The batch is the reference's: N_rand = 1024 rays plus one neighbour each (run_nerf.py:918-929), 64 + 128 samples.
 """
 import argparse
@@ -30,14 +33,18 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--ssr", type=int, default=-1, help="C >= 0: the SSR network with C classes through ssr.SSRRenderer instead")
 ap.add_argument("--loss", choices=("mse", "intrinsic"), default="mse", help="intrinsic: the reference's full loss, as torch expressions and in HIP")
 ap.add_argument("--optimizer", choices=("torch", "inerf"), default="torch", help="inerf: also time the step with optim.Adam (needs --loss intrinsic)")
+ap.add_argument("--batch", choices=("fixed", "inerf"), default="fixed", help="inerf: assemble the batch every step, reference expressions against batches.ObjectBatcher")
+ap.add_argument("--frame", type=int, default=400, help="frame size of --batch inerf")
 a = ap.parse_args()
 if a.optimizer == "inerf" and a.loss != "intrinsic":
     raise SystemExit("--optimizer inerf is timed next to torch.optim.Adam inside the --loss intrinsic alternation")
+if a.batch == "inerf" and (a.ssr >= 0 or a.loss != "mse" or a.optimizer != "torch"):
+    raise SystemExit("--batch inerf times the object-level step with the stand-in loss and torch.optim.Adam: not with --ssr, --loss intrinsic or --optimizer inerf")
 LOSS_WEIGHTS = {"image": 1.0, "chroma": 1.0, "sparsity": 0.01, "far": 0.01, "shading": 1.0, "residual": 1.0, "intensity": 0.1, "cluster": 1.0,
                 "semantic": 0.04}
 
 
-def time_both(steps, iters, what):
+def time_both(steps, iters, what, label="intrinsic loss as"):
     """``steps``: {name: step function}; warms every one up, then times them in alternating rounds and prints the medians."""
     import statistics
     for fn in steps.values():
@@ -51,7 +58,7 @@ def time_both(steps, iters, what):
                 fn()
             torch.cuda.synchronize(); times[k].append((time.perf_counter() - t0) / iters * 1e3)
     for k, v in times.items():
-        print(f"{what}, intrinsic loss as {k}: {statistics.median(v):.2f} ms per step (rounds: {', '.join(f'{x:.2f}' for x in v)})")
+        print(f"{what}, {label} {k}: {statistics.median(v):.2f} ms per step (rounds: {', '.join(f'{x:.2f}' for x in v)})")
 
 
 dev = torch.device("cuda:0")
@@ -138,6 +145,40 @@ def step():
     return float(loss.detach()) if False else loss
 
 
+if a.batch == "inerf":
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import torch_batches
+    from intrinsicnerf_amd import batches
+    rng = np.random.RandomState(0)
+    size, n_img = a.frame, 100
+    images = rng.rand(n_img, size, size, 3).astype(np.float32)
+    masks = (rng.rand(n_img, size, size, 1) > 0.3).astype(np.float32)
+    poses = np.tile(np.eye(4, dtype=np.float32), (n_img, 1, 1))
+    poses[:, :3, 3] = np.array([2.5, 1.5, 2.0], dtype=np.float32) + 0.1 * rng.randn(n_img, 3).astype(np.float32)
+    focal = 0.5 * size / np.tan(0.5 * 0.6911112070083618)
+    K = np.array([[focal, 0, 0.5 * size], [0, focal, 0.5 * size], [0, 0, 1]])
+    batcher = batches.ObjectBatcher(images, masks, poses, K, np.arange(n_img), n // 2, device=dev)
+    it = [0]
+
+    def from_reference():
+        it[0] += 1
+        return torch_batches.object_batch(it[0], images, masks, poses, K, np.arange(n_img), n // 2, 0, 0.5, dev)
+
+    def fed_step(get):
+        (rays_o, rays_d), target_s, target_m = get()                       # render()'s assembly of the batch (run_nerf.py:99-128)
+        viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
+        batch = torch.cat([rays_o, rays_d, 2 * torch.ones_like(rays_d[:, :1]), 6 * torch.ones_like(rays_d[:, :1]), viewdirs], -1)
+        ret = ol.render_rays(batch, net_c, q, 64, retraw=True, perturb=1.0, N_importance=128, network_fine=net_f, white_bkgd=True,
+                             raw_noise_std=0.0)
+        loss = (((ret["rgb_map"] - target_s) ** 2) * target_m).mean() + ((ret["rgb0"] - target_s) ** 2).mean()
+        opt.zero_grad(); loss.backward(); opt.step()
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        time_both({"the reference's expressions": lambda: fed_step(from_reference), "batches.ObjectBatcher": lambda: fed_step(batcher.next)},
+                  a.iters, f"training step (staged path), {n} rays x (64+128) samples, {size} x {size} frames", label="batch from")
+    sys.exit(0)
 if a.loss == "intrinsic":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import torch_losses
