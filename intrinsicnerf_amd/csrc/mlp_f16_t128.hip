@@ -27,6 +27,9 @@
 #ifndef INERF_T128_PEEL
 #define INERF_T128_PEEL 1       // (0: development builds for A/B runs)
 #endif
+#ifndef INERF_GATE_TRUNK_PARK
+#define INERF_GATE_TRUNK_PARK 1 // (0: development builds for A/B runs - the gated trunk evaluates the encoder again at the skip layer)
+#endif
 
 namespace inerf {
 
@@ -44,6 +47,17 @@ int64_t enc_cache_bytes_t128(int64_t n_points) {
     const int64_t tiles = (n_points + kPtsT - 1) / kPtsT;
     return (tiles < device_cus() ? tiles : device_cus()) * (int64_t)kEncCacheBytesT;
 }
+
+// Gated trunk (kMode == kGateTrunk below): the same 32 KiB parked in LDS instead.  The trunk kernel never runs the heads, so while its
+// layers run the 32 direction columns and the 8 pad halfs behind them (columns 256..295, 80 B per row and plane) are dead: five of a
+// row's eight sixteen-byte pieces go there, the other three into an extension area behind the two planes - piece (j - 5) of
+// [plane][row][3].  That is the CU's whole LDS: 151,552 + 12,288 = 163,840 B (the trunk kernel's launch size only).
+constexpr int kParkRowPieces = (kDirCols + 8) / 8;                       // 5: columns 256..295 of the piece's own row and plane
+constexpr int kParkExtPieces = kEncCols / 8 - kParkRowPieces;            // 3
+constexpr int kParkExtBytes = 2 * kPtsT * kParkExtPieces * 16;           // 12,288
+constexpr int kLdsBytesTrunk = kLdsBytesT + (INERF_GATE_TRUNK_PARK ? kParkExtBytes : 0);
+static_assert(kLdsBytesTrunk <= 160 * 1024, "the parked encoding must fit the CU's LDS");
+static_assert(kColDirD + 8 * kParkRowPieces <= kRowD && kParkRowPieces > 0 && kParkExtPieces >= 0, "parked pieces stay inside their row");
 
 int64_t sem_scratch_bytes_t128(int64_t n_points) {
     const int64_t tiles = (n_points + kPtsT - 1) / kPtsT;
@@ -68,7 +82,8 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 // kMode (density gate, object-level inference: DESIGN.md 3.1c) - the ONE tile body serves three kernels, so the gated pair computes
 // with the same instructions in the same order as the whole kernel:
 //   kWhole      encode, trunk, heads: everything of a tile, as above
-//   kGateTrunk  encode, trunk, then only sigma: raw[pt] = (0, 0, 0, sigma, 0 ...).  A point SURVIVES when !(sigma <= 0) (a NaN survives);
+//   kGateTrunk  encode (position only: nothing here reads the direction columns), trunk with the encoding parked in LDS for the skip layer
+//               (kPark below), then only sigma: raw[pt] = (0, 0, 0, sigma, 0 ...).  A point SURVIVES when !(sigma <= 0) (a NaN survives);
 //               the tile's survivors are counted by ballot, one lane reserves their contiguous record range with one atomicAdd on
 //               MlpParams.gate_count, and each survivor's h7 row leaves exactly as the epilogue left it in the planes (256 f16 hi |
 //               256 f16 lo = 1 KB, sixteen-byte stores) together with its point index
@@ -169,7 +184,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                     for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) { row[c] = (_Float16)0.0f; row[kPlaneT + c] = (_Float16)0.0f; }
                 }
             }
-            if (with_dir) {
+            if constexpr (kMode != kGateTrunk) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
                 const int fd = kParts - 1 - part;
                 if (fd < p.l_dir) {
                     const float s = (float)(1 << fd);
@@ -209,10 +224,10 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
 #ifdef INERF_ABL_NO_ENCODE      // (timing ablation of a development build: the first tile's encoding stays in LDS; results are wrong)
         if (tile == (int)blockIdx.x)
 #endif
-        encode(true);
+        encode(kMode != kGateTrunk);
         __syncthreads();
         // park the encoding for the skip layer (piece q = tid + 512 i of the tile's 2 048 sixteen-byte pieces: plane q / 1024, row (q % 1024) / 8)
-        const bool enc_cached = !kSsr && !kSave && kMode != kGateHeads && p.sem_scratch != nullptr;
+        const bool enc_cached = !kSsr && !kSave && kMode == kWhole && p.sem_scratch != nullptr;
         const __amdgpu_buffer_rsrc_t enc_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             p.sem_scratch, 0, enc_cached ? (int)((unsigned)gridDim.x * (unsigned)kEncCacheBytesT) : 0, 0x00020000);
         auto enc_piece = [&](int i) {
@@ -227,7 +242,40 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                                                            (int)blockIdx.x * kEncCacheBytesT + (tid + 512 * i) * 16, 0, 0);
             }
         }
+        // gated trunk: the same pieces parked in LDS (kParkRowPieces above) before layer 0's epilogue overwrites them - every wave's copy
+        // is read in front of that layer's first barrier; a thread parks and restores the SAME four pieces (piece j = tid & 7 of rows
+        // tid >> 3 and + 64 of both planes), so the parked copy needs no barrier of its own.  The pad words it covers hold the survivor
+        // counts only behind layer 7.  (Addresses from a laundered index, rebuilt at the skip layer instead of held across five layers.)
+        constexpr bool kPark = kMode == kGateTrunk && INERF_GATE_TRUNK_PARK;
+        auto park_copy = [&](bool restore) {
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            const int r = t >> 3, j = t & 7;
+            const bool in_row = j < kParkRowPieces;
+            _Float16* const cols = ldst + r * kRowD + j * 8;
+            _Float16* const parked = in_row ? cols + kColDirD : ldst + 2 * kPlaneT + (r * kParkExtPieces + (j - kParkRowPieces)) * 8;
+            u32x4 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int at_cols = (i >> 1) * kPlaneT + (i & 1) * 64 * kRowD;
+                const _Float16* const a = cols + at_cols;
+                const _Float16* const b = parked + (in_row ? at_cols : i * 64 * kParkExtPieces * 8);
+                v[i] = *reinterpret_cast<const u32x4*>(restore ? b : a);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int at_cols = (i >> 1) * kPlaneT + (i & 1) * 64 * kRowD;
+                _Float16* const a = cols + at_cols;
+                _Float16* const b = parked + (in_row ? at_cols : i * 64 * kParkExtPieces * 8);
+                *reinterpret_cast<u32x4*>(restore ? a : b) = v[i];
+            }
+        };
+        if constexpr (kPark) park_copy(false);
         auto encode_again = [&]() {         // the encoding back into columns 0..63 (sc0: past the vector L1, whose lines of an earlier tile may be stale)
+            if constexpr (kPark) {
+                park_copy(true);
+                return;
+            }
             if constexpr (!kSsr && !kSave) {
                 if (enc_cached) {
                     u32x4 v[4];
@@ -723,7 +771,7 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, h
     if (e != hipSuccess) return record(e);
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_heads_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
         if (e != hipSuccess) return record(e);
         attr_set.mark();
@@ -741,7 +789,7 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, h
         p.gate_idx = reinterpret_cast<int*>(ws + g.idx_off);
         p.gate_count = counts + s;
         const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
-        hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);
+        hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (+ the parked encoding's extension area)
         hipLaunchKernelGGL(k_mlp_gate_heads_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);      // (persistent: its tile count is on the device)
     }
     e = hipGetLastError();
