@@ -170,7 +170,8 @@ int inerf_encode_mlp_chunked(const inerf_net_desc* net, const float* packed_weig
  * Two slot formats:
  *   ROWS      a row-major fp32 [n_points, width] matrix.  save: 13; dz: 14.
  *   FRAGMENTS the operands of the 256-wide weight-gradient products dW = dZ^T X exactly as the matrix core consumes
- *             them: every value v is stored as f16 hi = f16(v') (towards zero) and f16 lo = f16(v' - hi) in 1 KB fragments
+ *             them: every value v is stored as f16 hi = f16(v') (towards zero; slots 0 and 1 of save, the encodings: to nearest,
+ *             so there lo may have the other sign) and f16 lo = f16(v' - hi) in 1 KB fragments
  *             [32 channels x 16 points]; with kb = 16-point block of the tile (0..3), cb = 32-channel block:
  *               byte offset = (((tile * 4 + kb) * 8 + cb) * 2 + (0: hi, 1: lo)) * 1024 + lane * 16 + 2 * i      (i = 0..7)
  *               channel = 32 cb + (lane & 31),  point = 64 tile + 32 (kb >> 1) + (i & 3) + 8 ((i >> 2) + 2 (kb & 1)) + 4 (lane >> 5)
@@ -200,7 +201,8 @@ int inerf_mlp_save_slot(const inerf_net_desc* net, int slot, int64_t n_points, i
 int inerf_mlp_save_slot_is_fragment(int slot, int gradient);
 int inerf_encode_mlp_train(const inerf_net_desc* net, const float* packed_weights, const float* rays, const float* z_vals,
                            int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, float* save_out,
-                           float* act_max /* optional device float the kernel max-es |activation| into (caller zeroes it) */,
+                           float* act_max /* optional device float the kernel max-es |activation| into (caller zeroes it): an upper bound of
+                                             every |value| the slots of save decode to, at most 2^-10 of it + 2^-27 above the largest */,
                            int32_t* status, void* stream);
 
 /* Transposed weights for the input-gradient chain, [host] -> [host] like inerf_pack_weights. */

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void k_encode_mlp_f16x3(const MlpParams p) 
         flag_f16_range(p, tile * kPts, kPts, amax, amax2, lane);
     }
     if (kSave && p.act_max) {             // bound of every saved activation (they were split as kActScale * value)
-        float m = fmaxf(amax, fmaxf((float)amax2[0], (float)amax2[1])) * (1.0f / kActScale);
+        float m = split_upper_bound(amax, amax2) * (1.0f / kActScale);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (lane == 0 && m == m) atomicMax(reinterpret_cast<unsigned int*>(p.act_max), __builtin_bit_cast(unsigned int, m));
@@ -704,7 +704,7 @@ __global__ __launch_bounds__(256, 2) void k_encode_mlp_f16x3_dual(const MlpParam
         flag_f16_range(p, tile * kPts, kPts, amax, amax2, lane_t);
     }
     if (kSave && p.act_max) {
-        float m = fmaxf(amax, fmaxf((float)amax2[0], (float)amax2[1])) * (1.0f / kActScale);
+        float m = split_upper_bound(amax, amax2) * (1.0f / kActScale);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (lane == 0 && m == m) atomicMax(reinterpret_cast<unsigned int*>(p.act_max), __builtin_bit_cast(unsigned int, m));

@@ -296,6 +296,18 @@ __device__ __forceinline__ float flag_f16_range(const MlpParams& p, int first_po
 }
 
 
+// What a training forward reports as act_max: an UPPER bound (scaled domain) of every value its activation buffer decodes to.  The
+// running maxima are not one: `amax` is the exact |t| of the values split_store split (hi to nearest: hi + lo lies within 2^-22 |t|,
+// or 2^-25, on either side of t) and `amax2` the largest |hi| of the layer outputs (hi towards zero: hi + lo <= |hi| + ulp(hi), which
+// is 2^-10 |hi|, or 2^-24 below f16's normal range) - a layer output of 14.502 was reported as 14.5.  The margins move the bound into
+// the next binade only from within themselves of a power of two.
+__device__ __forceinline__ float split_upper_bound(float amax, f16x2 amax2) {
+    const float h = fmaxf((float)amax2[0], (float)amax2[1]);
+    const float a = amax > 0.0f ? __builtin_fmaf(amax, 0x1p-21f, amax) + 0x1p-25f : amax;
+    const float b = h > 0.0f ? __builtin_fmaf(h, 0x1p-10f, h) + 0x1p-24f : h;
+    return fmaxf(a, b);
+}
+
 // running packed maximum of three: amax = maximum(amax, a, b) per f16 half in ONE instruction (v_pk_maximum3_f16, new in gfx950; IEEE
 // maximum: a NaN propagates into the maximum, where the range guard's `!(amax <= safe)` sees it).  Two v_pk_max_f16 before round 6.
 __device__ __forceinline__ void pk_max3_into(f16x2& amax, f16x2 a, f16x2 b) {

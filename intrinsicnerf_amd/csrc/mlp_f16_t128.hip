@@ -718,7 +718,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         // 128..255) and of the staging rows (lo plane, bytes 256..299) this tile's last readers may still be in)
     }
     if (kSave && p.act_max) {
-        float m = fmaxf(amax, fmaxf((float)amax2[0], (float)amax2[1])) * (1.0f / kActScale);
+        float m = split_upper_bound(amax, amax2) * (1.0f / kActScale);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         if (lane == 0 && m == m) atomicMax(reinterpret_cast<unsigned int*>(p.act_max), __builtin_bit_cast(unsigned int, m));
