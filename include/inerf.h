@@ -76,6 +76,13 @@ extern "C" {
 #define INERF_ENDPOINT_DIM    128
 #define INERF_RAY_FLOATS      11   /* o3 d3 near far viewdir3 (run_nerf.py:122-128, rays.py:251-255)       */
 #define INERF_MAX_CLASSES     240  /* semantic classes supported by the packed layout                     */
+/* Size limits of the per-ray stage kernels (one ray per 64-lane wavefront, its samples staged in LDS).  A shape outside
+ * them is INERF_E_UNSUPPORTED - checked first: for an empty batch too, whatever the pointers, before anything is launched. */
+#define INERF_MAX_SAMPLES     1024 /* inerf_composite[_backward]: samples per ray (16 chunks of 64)       */
+#define INERF_MIN_COARSE      3    /* inerf_sample_fine: coarse depths per ray (two mid-point bins)       */
+#define INERF_MAX_COARSE      256  /* inerf_sample_fine: coarse depths; inerf_sample_pdf: bins            */
+#define INERF_MIN_BINS        2    /* inerf_sample_pdf: bin edges per ray (one weight)                    */
+#define INERF_MAX_IMPORTANCE  512  /* inerf_sample_fine / inerf_sample_pdf: new samples per ray           */
 
 const char* inerf_version(void);
 int inerf_abi_version(void);          /* INERF_ABI_VERSION the library was built against */
@@ -305,7 +312,8 @@ int inerf_repack(const float* const* params, const int64_t* counts, int n_tensor
  * floats apart (3 for a [N,3] tensor, 11 for the d-part of a packed ray batch);
  * noise[N,S] (already scaled by raw_noise_std) or NULL.  n_classes / feat_dim select the optional
  * semantic (raw[...,11:11+C]) and endpoint-feature (the LAST feat_dim channels) sums.
- * Any output pointer may be NULL to skip it.  disp is NaN where acc == 0, as in the reference. */
+ * Any output pointer may be NULL to skip it.  disp is NaN where acc == 0, as in the reference.
+ * Limits: 1 <= S <= INERF_MAX_SAMPLES (forward and backward); any CH >= 11 + n_classes + feat_dim. */
 typedef struct inerf_composite_out {
     float* rgb;       /* [N,3] */
     float* disp;      /* [N]   */
@@ -340,13 +348,15 @@ int inerf_composite_backward(const float* raw, const float* z_vals, const float*
  * z_coarse[N,Sc], weights[N,Sc] (the full coarse weights; the kernel takes [1:-1] itself);
  * u: [n_importance] shared, or [N,n_importance] with INERF_FLAG_U_PER_RAY.
  * Outputs (any may be NULL): z_samples[N,n_importance], z_merged[N,Sc+n_importance] ascending,
- * z_std[N] (population std of the new samples).  Limits: 3 <= Sc <= 256, 1 <= n_importance <= 512. */
+ * z_std[N] (population std of the new samples).  Limits: INERF_MIN_COARSE (3) <= Sc <= INERF_MAX_COARSE (256),
+ * 1 <= n_importance <= INERF_MAX_IMPORTANCE (512). */
 int inerf_sample_fine(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int n_coarse,
                       int n_importance, uint32_t flags, float* z_samples, float* z_merged, float* z_std, void* stream);
 
 /* Stand-alone inverse-CDF sampler with the reference's own signature sample_pdf(bins, weights, N):
  * run_nerf_helpers.py:402-445 / rays.py:176-220.  bins[N,n_bins], weights[N,n_bins-1],
- * u as above -> samples[N,n_samples].  Limits: 2 <= n_bins <= 256, 1 <= n_samples <= 512. */
+ * u as above -> samples[N,n_samples].  Limits: INERF_MIN_BINS (2) <= n_bins <= INERF_MAX_COARSE (256),
+ * 1 <= n_samples <= INERF_MAX_IMPORTANCE (512). */
 int inerf_sample_pdf(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins, int n_samples,
                      uint32_t flags, float* samples, void* stream);
 
@@ -397,6 +407,9 @@ int64_t inerf_workspace_bytes(const inerf_net_desc* net, int64_t n_rays, int n_s
  * floats.  `workspace` / `workspace_bytes` of the argument are ignored.  May return 0 (workspace may then be NULL). */
 int64_t inerf_render_workspace_bytes(const inerf_render_args* args);
 
+/* Limits (the stage kernels' own, checked once before anything is enqueued - INERF_E_UNSUPPORTED): n_importance == 0:
+ * n_samples <= INERF_MAX_SAMPLES; n_importance > 0: INERF_MIN_COARSE <= n_samples <= INERF_MAX_COARSE and
+ * n_importance <= INERF_MAX_IMPORTANCE. */
 int inerf_render_rays(const inerf_render_args* args, void* stream);
 
 /* Raw channel counts for this network. */

@@ -21,6 +21,8 @@ FLAG_GATE_COLOUR = 32         # inerf_encode_mlp*: colour heads only on points w
 CLUSTER_IGNORE_LABEL = 1
 CAM_OPENGL = 1
 BASE_CHANNELS, ENDPOINT_DIM, RAY_FLOATS, MAX_CLASSES = 11, 128, 11, 240
+# size limits of the per-ray stage kernels (INERF_MAX_SAMPLES ... of include/inerf.h): E_UNSUPPORTED beyond them
+MAX_SAMPLES, MIN_COARSE, MAX_COARSE, MIN_BINS, MAX_IMPORTANCE = 1024, 3, 256, 2, 512
 
 _ERR = {E_INVALID: "invalid argument", E_UNSUPPORTED: "unsupported configuration",
         E_WORKSPACE: "workspace missing or too small", E_HIP: "HIP runtime error"}

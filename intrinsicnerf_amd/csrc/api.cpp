@@ -79,12 +79,22 @@ extern "C" int64_t inerf_render_workspace_bytes(const inerf_render_args* a) {
     return plan(a->net, a->n_rays, a->n_samples, a->n_importance, a->flags, provided(*a)).total;
 }
 
+// The stage kernels' size limits for this pair of sample counts (include/inerf.h), so that a batch none of whose later stages can run
+// is turned away before the first one is enqueued.
+static bool sizes_supported(int sc, int ni) {
+    static_assert(INERF_MAX_COARSE + INERF_MAX_IMPORTANCE <= INERF_MAX_SAMPLES, "the fine pass composites n_samples + n_importance");
+    if (ni <= 0) return sc <= INERF_MAX_SAMPLES;                                      // inerf_composite alone
+    return sc >= INERF_MIN_COARSE && sc <= INERF_MAX_COARSE && ni <= INERF_MAX_IMPORTANCE;   // inerf_sample_fine; the merged count then fits
+}
+
 extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) {
-    if (a && a->n_rays == 0) return inerf::net_supported(a->net) ? INERF_OK : INERF_E_UNSUPPORTED;   // empty batch: null pointers allowed
+    if (a && a->n_rays == 0)                                                          // empty batch: null pointers allowed
+        return inerf::net_supported(a->net) && sizes_supported(a->n_samples, a->n_importance) ? INERF_OK : INERF_E_UNSUPPORTED;
     if (!a || !a->packed_coarse || !a->rays || !a->t_vals || a->n_rays < 0 || a->n_samples < 1 || a->n_importance < 0)
         return INERF_E_INVALID;
     if (!inerf::net_supported(a->net)) return INERF_E_UNSUPPORTED;
     if (a->n_importance > 0 && !a->u) return INERF_E_INVALID;
+    if (!sizes_supported(a->n_samples, a->n_importance)) return INERF_E_UNSUPPORTED;
     const Plan p = plan(a->net, a->n_rays, a->n_samples, a->n_importance, a->flags, provided(*a));
     if (p.total > 0 && (!a->workspace || a->workspace_bytes < p.total)) return INERF_E_WORKSPACE;
     char* ws = static_cast<char*>(a->workspace);

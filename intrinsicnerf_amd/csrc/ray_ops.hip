@@ -58,7 +58,8 @@ __global__ __launch_bounds__(256) void k_sample_coarse(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // compositing: one ray per wave; sample s of chunk c sits in lane s - 64*c
 // ------------------------------------------------------------------------------------------------
-constexpr int kMaxChunks = 16;     // up to 1024 samples per ray
+constexpr int kMaxChunks = INERF_MAX_SAMPLES / 64;     // 16: up to 1024 samples per ray
+static_assert(INERF_MAX_SAMPLES % 64 == 0, "whole chunks");
 
 __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw, const float* __restrict__ z,
                                                    const float* __restrict__ rays_d, int d_stride,
@@ -324,8 +325,9 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // hierarchical resampling + merge: one ray per wave, everything staged in LDS
 // ------------------------------------------------------------------------------------------------
-constexpr int kMaxCoarse = 256;
-constexpr int kMaxImportance = 512;
+constexpr int kMaxCoarse = INERF_MAX_COARSE;
+constexpr int kMaxImportance = INERF_MAX_IMPORTANCE;
+static_assert(INERF_MIN_BINS >= 2 && INERF_MIN_COARSE == INERF_MIN_BINS + 1, "at least one pdf weight; the mid-points are one fewer than the depths");
 
 struct FineSmem {
     float cdf[kMaxCoarse];
@@ -488,13 +490,12 @@ extern "C" int inerf_composite(const float* raw, const float* z_vals, const floa
                                const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim,
                                uint32_t flags, const inerf_composite_out* out, void* stream) {
     using namespace inerf;
+    if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;    // a property of the shape: for an empty batch too, whatever the pointers
     if (n_rays == 0 && out) return INERF_OK;
     if (!raw || !z_vals || !rays_d || !out || n_rays < 0 || n_samples < 1 || rays_d_stride < 3) return INERF_E_INVALID;
     if (channels < INERF_BASE_CHANNELS || n_classes < 0 || feat_dim < 0 ||
         INERF_BASE_CHANNELS + n_classes + feat_dim > channels)
         return INERF_E_INVALID;
-    if (n_samples > 64 * kMaxChunks) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0) return INERF_OK;
     const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_composite, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
@@ -508,11 +509,10 @@ extern "C" int inerf_composite_backward(const float* raw, const float* z_vals, c
                                         int feat_dim, uint32_t flags, const inerf_composite_out* grads, float* d_raw,
                                         void* stream) {
     using namespace inerf;
+    if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;
     if (n_rays == 0 && grads) return INERF_OK;
     if (!raw || !z_vals || !rays_d || !grads || !d_raw || n_rays < 0 || n_samples < 1 || rays_d_stride < 3) return INERF_E_INVALID;
     if (channels < INERF_BASE_CHANNELS + n_classes + feat_dim || n_classes < 0 || feat_dim < 0) return INERF_E_INVALID;
-    if (n_samples > 64 * kMaxChunks) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0) return INERF_OK;
     const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_composite_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
@@ -525,10 +525,10 @@ extern "C" int inerf_sample_fine(const float* z_coarse, const float* weights, co
                                  int n_importance, uint32_t flags, float* z_samples, float* z_merged, float* z_std,
                                  void* stream) {
     using namespace inerf;
+    // the limits are a property of the shape: they hold for an empty batch too, whatever the pointers
+    if (n_coarse < INERF_MIN_COARSE || n_coarse > kMaxCoarse || n_importance < 1 || n_importance > kMaxImportance) return INERF_E_UNSUPPORTED;
     if (n_rays == 0) return INERF_OK;
     if (!z_coarse || !weights || !u || n_rays < 0) return INERF_E_INVALID;
-    if (n_coarse < 3 || n_coarse > kMaxCoarse || n_importance < 1 || n_importance > kMaxImportance) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0) return INERF_OK;
     const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_sample_fine<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z_coarse, weights, u,
@@ -540,10 +540,10 @@ extern "C" int inerf_sample_fine(const float* z_coarse, const float* weights, co
 extern "C" int inerf_sample_pdf(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins,
                                 int n_samples, uint32_t flags, float* samples, void* stream) {
     using namespace inerf;
+    // (a [N, 0] weights tensor of a single bin edge has no storage: the size is what is wrong with it, not its null pointer)
+    if (n_bins < INERF_MIN_BINS || n_bins > kMaxCoarse || n_samples < 1 || n_samples > kMaxImportance) return INERF_E_UNSUPPORTED;
     if (n_rays == 0) return INERF_OK;
     if (!bins || !weights || !u || !samples || n_rays < 0) return INERF_E_INVALID;
-    if (n_bins < 2 || n_bins > kMaxCoarse || n_samples < 1 || n_samples > kMaxImportance) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0) return INERF_OK;
     const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_sample_fine<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bins, weights, u,
