@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40013
+#define INERF_ABI_VERSION 40014
 
 /* error codes */
 #define INERF_OK              0
@@ -414,6 +414,77 @@ int inerf_render_rays(const inerf_render_args* args, void* stream);
 
 /* Raw channel counts for this network. */
 int inerf_raw_channels(const inerf_net_desc* net, uint32_t flags, int fine);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training draws: the random tensors of a training-mode render, drawn inside the kernels.
+ * Replaces the stratified jitter t_rand[N,S] (run_nerf.py:472-486, trainer.py:737-746), the density noise
+ * randn * raw_noise_std of both passes (run_nerf.py:386-387, model_utils.py:70-72) and the inverse-CDF variates u[N,Ni]
+ * (run_nerf_helpers.py:410-414, rays.py:194-197).  A sample's draw is a pure function of (seed, step, stream, global ray index,
+ * sample index): the same batch gives the same bits for any chunking and any split of the rays over callers, and a backward pass
+ * regenerates the noise its forward added instead of keeping it.  (torch's own random streams are not reproduced.)
+ *
+ * Philox4x32-10 as Random123 defines it (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds):
+ *   key     = {seed & 0xffffffff, seed >> 32}
+ *   counter = {ray, block | (stream << 16), step & 0xffffffff, step >> 32}
+ *     ray    = ray_base + the ray's index in this call, an unsigned 32-bit value;
+ *     block  = sample >> 2: the four output words belong to samples 4 block .. 4 block + 3 (sample < INERF_MAX_SAMPLES, block < 256);
+ *     stream = INERF_DRAW_STREAM_*.
+ *   uniform (jitter, u):  (word >> 8) * 2^-24 - in [0, 1) on torch.rand's fp32 lattice, never 1.
+ *   normal (the noise streams): Box-Muller on the word pairs (0, 1) and (2, 3):
+ *     u1 = ((w_even >> 9) + 1) * 2^-23 in (0, 1], u2 = (w_odd >> 8) * 2^-24, r = sqrtf(-2 logf(u1)), theta = fp32(2 pi) * u2;
+ *     the pair's even sample is r cosf(theta), its odd sample r sinf(theta) (accurate library functions); |z| < 5.65.
+ *     The noise added to sigma is z * noise_std, rounded once, as randn * std is.
+ * step: the host value, or *step_dev (DEVICE, one int64, 8-byte aligned) when that is not NULL.  No drawing kernel writes it:
+ *   inerf_draw_advance is a launch of its own (one workgroup) that adds 1, so a captured step draws anew at every replay.
+ * Every drawn entry point takes the arguments of its classic form plus an inerf_draw_args; the classic random-tensor pointers must be
+ * NULL there (INERF_E_INVALID otherwise, as for a misaligned step_dev, a negative or non-finite noise_std or a flag that means nothing
+ * to the entry point: INERF_DRAW_PERTURB is inerf_render_rays_drawn's alone, INERF_DRAW_FINE the two composite calls'), and
+ * ray_base + n_rays > 2^32 is INERF_E_UNSUPPORTED - all checked before anything is enqueued, for an empty batch too.  A drawn call and
+ * the classic call fed with inerf_draw_fill's tensors give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+#define INERF_DRAW_STREAM_JITTER        0
+#define INERF_DRAW_STREAM_NOISE_COARSE  1
+#define INERF_DRAW_STREAM_U             2
+#define INERF_DRAW_STREAM_NOISE_FINE    3
+#define INERF_DRAW_PERTURB  1u   /* inerf_render_rays_drawn: perturb > 0 - jitter the coarse depths, per-ray random u            */
+#define INERF_DRAW_FINE     2u   /* inerf_composite[_backward]_drawn: the fine pass's noise stream (3) instead of the coarse (1) */
+typedef struct inerf_draw_args {
+    uint64_t seed;
+    int64_t step;
+    const int64_t* step_dev;
+    uint64_t ray_base;
+    float noise_std;
+    uint32_t flags;
+} inerf_draw_args;
+
+/* out[n_rays, n_per_ray] = one stream as the tensor the classic entry points take (the noise streams already scaled by noise_std):
+ * the test instrument, and the way to look at what a drawn call used.  1 <= n_per_ray <= INERF_MAX_SAMPLES. */
+int inerf_draw_fill(const inerf_draw_args* draw, int stream_id, int64_t n_rays, int n_per_ray, float* out, void* stream);
+/* *step_dev += 1 (one workgroup, one plain store). */
+int inerf_draw_advance(int64_t* step_dev, void* stream);
+
+/* inerf_sample_coarse with the jitter drawn (stream 0); t_rand must be NULL.  n_samples <= INERF_MAX_SAMPLES. */
+int inerf_sample_coarse_drawn(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int n_samples,
+                              uint32_t flags, float* z_out, const inerf_draw_args* draw, void* stream);
+/* inerf_composite / inerf_composite_backward with the noise regenerated (stream 1, or 3 with INERF_DRAW_FINE); noise must be NULL. */
+int inerf_composite_drawn(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride, const float* noise,
+                          int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim, uint32_t flags,
+                          const inerf_composite_out* out, const inerf_draw_args* draw, void* stream);
+int inerf_composite_backward_drawn(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
+                                   const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes,
+                                   int feat_dim, uint32_t flags, const inerf_composite_out* grads, float* d_raw,
+                                   const inerf_draw_args* draw, void* stream);
+/* inerf_sample_fine / inerf_sample_pdf with per-ray u drawn (stream 2; the unsorted-u path of INERF_FLAG_U_PER_RAY); u must be NULL. */
+int inerf_sample_fine_drawn(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int n_coarse,
+                            int n_importance, uint32_t flags, float* z_samples, float* z_merged, float* z_std,
+                            const inerf_draw_args* draw, void* stream);
+int inerf_sample_pdf_drawn(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins, int n_samples,
+                           uint32_t flags, float* samples, const inerf_draw_args* draw, void* stream);
+/* inerf_render_rays in training mode without an RNG of the caller's: t_rand, noise_coarse and noise_fine of `args` must be NULL.
+ * INERF_DRAW_PERTURB (perturb > 0): the coarse depths are jittered and u is drawn per ray - args->u must be NULL; without it nothing
+ * is drawn that the reference does not draw: args->u is the caller's (shared linspace) u as in the classic form.  noise_std > 0
+ * (raw_noise_std): both passes add drawn noise - and are then not gated, as a pass with a noise tensor is not. */
+int inerf_render_rays_drawn(const inerf_render_args* args, const inerf_draw_args* draw, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Image-level neighbours of the path.

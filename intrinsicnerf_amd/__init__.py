@@ -4,6 +4,7 @@
   ssr            drop-in for SSR/ + train_SSR_main.py's render path (SSRRenderMixin, Semantic_NeRF, ...)
   losses         the trainers' loss terms, one forward and one backward launch (compute_intrinsic_loss, *_step_loss)
   optim          the trainers' optimizer.step(): Adam as one launch of the library (optim.Adam)
+  draws          the training step's random variates drawn in the kernels (DrawState; opt-in)
   kernels        tensor-level launchers of the C ABI (include/inerf.h, libinerf.so)
   packing        state dict -> MFMA-fragment-ordered weight blob
   distributed    ray sharding across the GPUs of a node + RCCL gather of the rendered maps
@@ -15,6 +16,8 @@ device the render entry points raise.
 from . import _capi, kernels, packing  # noqa: F401
 from . import object_level, ssr  # noqa: F401
 from . import optim  # noqa: F401
+from . import draws  # noqa: F401
+from .draws import DrawState  # noqa: F401
 from .optim import Adam  # noqa: F401
 
 __version__ = "0.1.0"

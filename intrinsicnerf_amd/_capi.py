@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40013          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40014          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -106,6 +106,15 @@ BATCH_DRAW, BATCH_ADVANCE, BATCH_OPENGL = 1, 2, 4
 BATCH_STATUS_WALK, BATCH_STATUS_INDEX = 1, 2
 BATCH_MAX_WALK = 64
 
+class DrawArgs(C.Structure):
+    """inerf_draw_args: the training draws (include/inerf.h, "Training draws")."""
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_int64), ("step_dev", C.c_void_p), ("ray_base", C.c_uint64),
+                ("noise_std", C.c_float), ("flags", C.c_uint32)]
+
+
+DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
+DRAW_PERTURB, DRAW_FINE = 1, 2
+
 ADAM_TABLE_TENSORS = 72      # tensors per launch of inerf_adam_step (its by-value kernel-argument table)
 
 LOSS_KEY_LABELS, LOSS_MASK_OUTER = 1, 2
@@ -177,6 +186,15 @@ SYMBOLS = {
     "inerf_intrinsic_loss_backward": (_I, [C.POINTER(LossArgs), _P]),
     "inerf_adam_step": (_I, [C.POINTER(AdamArgs), _P]),
     "inerf_batch_assemble": (_I, [C.POINTER(BatchArgs), _P]),
+    "inerf_draw_fill": (_I, [C.POINTER(DrawArgs), _I, _L, _I, _P, _P]),
+    "inerf_draw_advance": (_I, [_P, _P]),
+    "inerf_sample_coarse_drawn": (_I, [_P, _P, _P, _L, _I, _U, _P, C.POINTER(DrawArgs), _P]),
+    "inerf_composite_drawn": (_I, [_P, _P, _P, _I, _P, _L, _I, _I, _I, _I, _U, C.POINTER(CompositeOut), C.POINTER(DrawArgs), _P]),
+    "inerf_composite_backward_drawn": (_I, [_P, _P, _P, _I, _P, _L, _I, _I, _I, _I, _U, C.POINTER(CompositeOut), _P,
+                                            C.POINTER(DrawArgs), _P]),
+    "inerf_sample_fine_drawn": (_I, [_P, _P, _P, _L, _I, _I, _U, _P, _P, _P, C.POINTER(DrawArgs), _P]),
+    "inerf_sample_pdf_drawn": (_I, [_P, _P, _P, _L, _I, _I, _U, _P, C.POINTER(DrawArgs), _P]),
+    "inerf_render_rays_drawn": (_I, [C.POINTER(RenderArgs), C.POINTER(DrawArgs), _P]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "draws.h"
 #include "layout.h"
 
 namespace {
@@ -87,13 +88,21 @@ static bool sizes_supported(int sc, int ni) {
     return sc >= INERF_MIN_COARSE && sc <= INERF_MAX_COARSE && ni <= INERF_MAX_IMPORTANCE;   // inerf_sample_fine; the merged count then fits
 }
 
-extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) {
+// `d` null: the classic form.  Otherwise the drawn form: what the reference draws comes from the kernels (include/inerf.h, "Training draws").
+static int render_impl(const inerf_render_args* a, const inerf_draw_args* d, void* stream) {
+    const bool perturb = d && (d->flags & INERF_DRAW_PERTURB);
+    const bool drawn_noise = d && d->noise_std > 0.0f;
+    if (d) {
+        if (!a) return INERF_E_INVALID;
+        if (const int rc = inerf::draw_check(d, a->n_rays, INERF_DRAW_PERTURB)) return rc;
+        if (a->t_rand || a->noise_coarse || a->noise_fine || (perturb && a->u)) return INERF_E_INVALID;
+    }
     if (a && a->n_rays == 0)                                                          // empty batch: null pointers allowed
         return inerf::net_supported(a->net) && sizes_supported(a->n_samples, a->n_importance) ? INERF_OK : INERF_E_UNSUPPORTED;
     if (!a || !a->packed_coarse || !a->rays || !a->t_vals || a->n_rays < 0 || a->n_samples < 1 || a->n_importance < 0)
         return INERF_E_INVALID;
     if (!inerf::net_supported(a->net)) return INERF_E_UNSUPPORTED;
-    if (a->n_importance > 0 && !a->u) return INERF_E_INVALID;
+    if (a->n_importance > 0 && !a->u && !perturb) return INERF_E_INVALID;
     if (!sizes_supported(a->n_samples, a->n_importance)) return INERF_E_UNSUPPORTED;
     const Plan p = plan(a->net, a->n_rays, a->n_samples, a->n_importance, a->flags, provided(*a));
     if (p.total > 0 && (!a->workspace || a->workspace_bytes < p.total)) return INERF_E_WORKSPACE;
@@ -107,35 +116,56 @@ extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) {
 
     // ---- coarse pass ----
     float* z_c = a->z_coarse ? a->z_coarse : f(p.z_c);
-    rc = inerf_sample_coarse(a->rays, a->t_vals, a->t_rand, n, sc, a->flags, z_c, stream);
+    inerf_draw_args dn{};                          // the stage calls' draw arguments: no flag but INERF_DRAW_FINE for the fine pass's noise
+    if (d) {
+        dn = *d;
+        dn.flags = 0;
+    }
+    rc = perturb ? inerf_sample_coarse_drawn(a->rays, a->t_vals, nullptr, n, sc, a->flags, z_c, &dn, stream)
+                 : inerf_sample_coarse(a->rays, a->t_vals, a->t_rand, n, sc, a->flags, z_c, stream);
     if (rc) return rc;
     float* raw_c = a->raw_coarse ? a->raw_coarse : f(p.raw_c);
     // the coarse net never emits the endpoint feature (trainer.py:751-755: endpoint_feat=False)
     const uint32_t mlp_flags = a->flags & ~INERF_FLAG_GATE_COLOUR;
     rc = inerf_encode_mlp_chunked(&a->net, a->packed_coarse, a->rays, z_c, n, sc,
-                                  (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr), raw_c, a->status,
+                                  (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr || drawn_noise), raw_c, a->status,
                                   a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
     if (rc) return rc;
     inerf_composite_out oc = a->coarse;
     oc.feat = nullptr;
     if (ni > 0 && !oc.weights) oc.weights = f(p.w_c);
-    rc = inerf_composite(raw_c, z_c, a->rays + 3, INERF_RAY_FLOATS, a->noise_coarse, n, sc, p.ch_c, oc.sem ? n_cls : 0, 0,
-                         a->flags, &oc, stream);
+    rc = drawn_noise ? inerf_composite_drawn(raw_c, z_c, a->rays + 3, INERF_RAY_FLOATS, nullptr, n, sc, p.ch_c, oc.sem ? n_cls : 0, 0,
+                                             a->flags, &oc, &dn, stream)
+                     : inerf_composite(raw_c, z_c, a->rays + 3, INERF_RAY_FLOATS, a->noise_coarse, n, sc, p.ch_c, oc.sem ? n_cls : 0, 0,
+                                       a->flags, &oc, stream);
     if (rc || ni == 0) return rc;
 
     // ---- resample, fine pass ----
     float* z_s = a->z_samples ? a->z_samples : f(p.z_s);
     float* z_f = a->z_fine ? a->z_fine : f(p.z_f);
-    rc = inerf_sample_fine(z_c, oc.weights, a->u, n, sc, ni, a->flags, z_s, z_f, a->z_std, stream);
+    rc = perturb ? inerf_sample_fine_drawn(z_c, oc.weights, nullptr, n, sc, ni, a->flags, z_s, z_f, a->z_std, &dn, stream)
+                 : inerf_sample_fine(z_c, oc.weights, a->u, n, sc, ni, a->flags, z_s, z_f, a->z_std, stream);
     if (rc) return rc;
     float* raw_f = a->raw_fine ? a->raw_fine : f(p.raw_f);
     const float* w_fine = a->packed_fine ? a->packed_fine : a->packed_coarse;   // run_nerf.py:506
-    rc = inerf_encode_mlp_chunked(&a->net, w_fine, a->rays, z_f, n, p.s_f, mlp_flags | gate_flag(a->raw_fine != nullptr, a->noise_fine != nullptr), raw_f,
+    rc = inerf_encode_mlp_chunked(&a->net, w_fine, a->rays, z_f, n, p.s_f, mlp_flags | gate_flag(a->raw_fine != nullptr, a->noise_fine != nullptr || drawn_noise), raw_f,
                                   a->status, a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
     if (rc) return rc;
     const bool ep = ssr && (a->flags & INERF_FLAG_ENDPOINT);
     inerf_composite_out of = a->fine;
     if (!ep) of.feat = nullptr;
+    if (drawn_noise) {
+        dn.flags = INERF_DRAW_FINE;
+        return inerf_composite_drawn(raw_f, z_f, a->rays + 3, INERF_RAY_FLOATS, nullptr, n, p.s_f, p.ch_f, of.sem ? n_cls : 0,
+                                     (ep && of.feat) ? INERF_ENDPOINT_DIM : 0, a->flags, &of, &dn, stream);
+    }
     return inerf_composite(raw_f, z_f, a->rays + 3, INERF_RAY_FLOATS, a->noise_fine, n, p.s_f, p.ch_f, of.sem ? n_cls : 0,
                            (ep && of.feat) ? INERF_ENDPOINT_DIM : 0, a->flags, &of, stream);
+}
+
+extern "C" int inerf_render_rays(const inerf_render_args* a, void* stream) { return render_impl(a, nullptr, stream); }
+
+extern "C" int inerf_render_rays_drawn(const inerf_render_args* a, const inerf_draw_args* draw, void* stream) {
+    if (!draw) return INERF_E_INVALID;
+    return render_impl(a, draw, stream);
 }

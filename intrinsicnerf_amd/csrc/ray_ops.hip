@@ -8,6 +8,7 @@
 // instruction count.  Built with -ffp-contract=off: every mul/add rounds like the reference's.
 #include <hip/hip_runtime.h>
 
+#include "draws.h"
 #include "layout.h"
 
 namespace inerf {
@@ -34,22 +35,29 @@ __device__ __forceinline__ float depth_at(float near, float far, float t, bool l
     return __fdiv_rn(1.0f, __fadd_rn(a, b));
 }
 
+// kDrawn: the jitter is drawn in the kernel (draws.h, stream 0) instead of read from t_rand; the classic instantiation is unchanged.
+template <bool kDrawn>
 __global__ __launch_bounds__(256) void k_sample_coarse(const float* __restrict__ rays, const float* __restrict__ t_vals,
                                                        const float* __restrict__ t_rand, long long n_rays, int s_count,
-                                                       int lindisp, float* __restrict__ z_out) {
+                                                       int lindisp, float* __restrict__ z_out, DrawParams dp) {
     const long long total = n_rays * s_count;
+    long long step = 0;
+    if constexpr (kDrawn) step = draw_step(dp);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long ray = i / s_count;
         const int s = (int)(i - ray * s_count);
         const float near = rays[ray * INERF_RAY_FLOATS + 6], far = rays[ray * INERF_RAY_FLOATS + 7];
         const float zc = depth_at(near, far, t_vals[s], lindisp != 0);
         float z = zc;
-        if (t_rand) {   // stratified jitter inside [lower, upper] (run_nerf.py:472-486)
+        if (kDrawn || t_rand) {   // stratified jitter inside [lower, upper] (run_nerf.py:472-486)
             const float zp = s > 0 ? depth_at(near, far, t_vals[s - 1], lindisp != 0) : zc;
             const float zn = s + 1 < s_count ? depth_at(near, far, t_vals[s + 1], lindisp != 0) : zc;
             const float lower = s > 0 ? __fmul_rn(0.5f, __fadd_rn(zc, zp)) : zc;
             const float upper = s + 1 < s_count ? __fmul_rn(0.5f, __fadd_rn(zn, zc)) : zc;
-            z = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), t_rand[i]));
+            float tr;
+            if constexpr (kDrawn) tr = draw_uniform(dp, step, ray, s);
+            else tr = t_rand[i];
+            z = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), tr));
         }
         z_out[i] = z;
     }
@@ -61,13 +69,18 @@ __global__ __launch_bounds__(256) void k_sample_coarse(const float* __restrict__
 constexpr int kMaxChunks = INERF_MAX_SAMPLES / 64;     // 16: up to 1024 samples per ray
 static_assert(INERF_MAX_SAMPLES % 64 == 0, "whole chunks");
 
+// kDrawn: the density noise is regenerated in the kernel (draws.h, stream 1 or 3; every lane computes the Philox block of its own sample - ~60
+// integer instructions next to 44 B of raw and an expf) instead of read from `noise`; the classic instantiation is unchanged.
+template <bool kDrawn>
 __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw, const float* __restrict__ z,
                                                    const float* __restrict__ rays_d, int d_stride,
                                                    const float* __restrict__ noise, long long n_rays, int s_count, int ch,
-                                                   int n_classes, int feat_dim, int white_bkgd, inerf_composite_out out) {
+                                                   int n_classes, int feat_dim, int white_bkgd, inerf_composite_out out, DrawParams dp) {
     const int lane = threadIdx.x & 63;
     const long long ray = blockIdx.x * (long long)kRaysPerBlock + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
+    long long step = 0;
+    if constexpr (kDrawn) step = draw_step(dp);
     const float* __restrict__ rr = raw + ray * (long long)s_count * ch;
     const float* __restrict__ zr = z + ray * (long long)s_count;
     const float* d = rays_d + ray * (long long)d_stride;
@@ -98,7 +111,8 @@ __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ raw
             const float gap = s + 1 < s_count ? __fsub_rn(zr[s + 1], zz) : 1e10f;
             const float dist = __fmul_rn(gap, dnorm);
             float sigma = v[3];
-            if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
+            if constexpr (kDrawn) sigma = __fadd_rn(sigma, draw_noise(dp, step, ray, s));
+            else if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
             // alpha = 1 - exp(-relu(sigma) * dist)                   (run_nerf.py:372,395)
             alpha = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(sigma, 0.0f), dist)));
             if (sigma != sigma) alpha = sigma;                         // relu(NaN) stays NaN in torch
@@ -196,14 +210,17 @@ __device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& tota
     return incl - v;
 }
 
+template <bool kDrawn>
 __global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__ raw, const float* __restrict__ z,
                                                        const float* __restrict__ rays_d, int d_stride,
                                                        const float* __restrict__ noise, long long n_rays, int s_count, int ch,
                                                        int n_classes, int feat_dim, int white_bkgd, inerf_composite_out g,
-                                                       float* __restrict__ d_raw) {
+                                                       float* __restrict__ d_raw, DrawParams dp) {
     const int lane = threadIdx.x & 63;
     const long long ray = blockIdx.x * (long long)kRaysPerBlock + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
+    long long step = 0;
+    if constexpr (kDrawn) step = draw_step(dp);
     const float* __restrict__ rr = raw + ray * (long long)s_count * ch;
     const float* __restrict__ zr = z + ray * (long long)s_count;
     float* __restrict__ dr = d_raw + ray * (long long)s_count * ch;
@@ -227,7 +244,8 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__
             const float gap = s + 1 < s_count ? __fsub_rn(zr[s + 1], zz) : 1e10f;
             const float dist = __fmul_rn(gap, dnorm);
             float sigma = rr[(long long)s * ch + 3];
-            if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
+            if constexpr (kDrawn) sigma = __fadd_rn(sigma, draw_noise(dp, step, ray, s));
+            else if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
             alpha = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(sigma, 0.0f), dist)));
             if (sigma != sigma) alpha = sigma;
         }
@@ -309,7 +327,8 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__
             const float gap = s + 1 < s_count ? __fsub_rn(zr[s + 1], zr[s]) : 1e10f;
             const float dist = __fmul_rn(gap, dnorm);
             float sigma = rs[3];
-            if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
+            if constexpr (kDrawn) sigma = __fadd_rn(sigma, draw_noise(dp, step, ray, s));
+            else if (noise) sigma = __fadd_rn(sigma, noise[ray * (long long)s_count + s]);
             // d alpha / d sigma = dist * exp(-sigma * dist) for sigma > 0 (relu: zero at and below 0); NaN stays NaN
             float d_sigma = sigma > 0.0f ? d_alpha * (dist * expf(-__fmul_rn(sigma, dist))) : 0.0f;
             if (sigma != sigma) d_sigma = sigma;
@@ -346,16 +365,19 @@ __device__ __forceinline__ bool less_nan_last(float a, float b) {
 //                   pdf over weights[1:-1], merged + sorted output).
 // kDirect = true : the stand-alone sample_pdf(bins, weights, N) signature: z_coarse is bins[N,sc],
 //                   weights is [N,sc-1]; no merge.
-template <bool kDirect>
+// kDrawn: per-ray u drawn in the kernel (draws.h, stream 2) - the unsorted-u path INERF_FLAG_U_PER_RAY takes.
+template <bool kDirect, bool kDrawn>
 __global__ __launch_bounds__(256) void k_sample_fine(const float* __restrict__ z_coarse, const float* __restrict__ weights,
                                                      const float* __restrict__ u, int u_per_ray, long long n_rays, int sc,
                                                      int ni, float* __restrict__ z_samples, float* __restrict__ z_merged,
-                                                     float* __restrict__ z_std) {
+                                                     float* __restrict__ z_std, DrawParams dp) {
     __shared__ FineSmem smem[kRaysPerBlock];
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const long long ray = blockIdx.x * (long long)kRaysPerBlock + wv;
     if (ray >= n_rays) return;             // whole wave exits together; no block-level barrier is used below
+    long long step = 0;
+    if constexpr (kDrawn) step = draw_step(dp);
     FineSmem& sm = smem[wv];
     const float* __restrict__ zr = z_coarse + ray * (long long)sc;
     const int nb = kDirect ? sc : sc - 1;  // bins = z mid-points              (run_nerf.py:499)
@@ -390,7 +412,9 @@ __global__ __launch_bounds__(256) void k_sample_fine(const float* __restrict__ z
     // inverse CDF                                                              (run_nerf_helpers.py:427-443)
     float s1 = 0.0f;
     for (int j = lane; j < ni; j += 64) {
-        const float uu = u_per_ray ? u[ray * (long long)ni + j] : u[j];
+        float uu;
+        if constexpr (kDrawn) uu = draw_uniform(dp, step, ray, j);
+        else uu = u_per_ray ? u[ray * (long long)ni + j] : u[j];
         // searchsorted(cdf, u, right=True): number of cdf entries <= u
         int lo = 0, hi = nb;
         while (lo < hi) {
@@ -473,24 +497,59 @@ __global__ __launch_bounds__(256) void k_sample_fine(const float* __restrict__ z
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-extern "C" int inerf_sample_coarse(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays,
-                                   int n_samples, uint32_t flags, float* z_out, void* stream) {
-    using namespace inerf;
+namespace inerf {
+
+// kernels that materialise / advance the draws
+__global__ __launch_bounds__(256) void k_draw_fill(float* __restrict__ out, long long n_rays, int n_per_ray, DrawParams dp) {
+    const long long total = n_rays * n_per_ray;
+    const long long step = draw_step(dp);
+    const bool normal = (dp.stream & 1u) != 0;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long ray = i / n_per_ray;
+        const int s = (int)(i - ray * n_per_ray);
+        out[i] = normal ? draw_noise(dp, step, ray, s) : draw_uniform(dp, step, ray, s);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_draw_advance(long long* step) {
+    if (threadIdx.x == 0) *step = *step + 1;
+}
+
+// One body per stage for the classic and the drawn entry point: `d` null = classic.  The shape limits come first (they hold for an
+// empty batch too, whatever the pointers), then - drawn only - the draw arguments and the classic random pointer, which must be NULL.
+static int sample_coarse_impl(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays, int n_samples,
+                              uint32_t flags, float* z_out, const inerf_draw_args* d, bool drawn, void* stream) {
+    if (drawn) {
+        if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;       // the counter's block field
+        if (const int rc = draw_check(d, n_rays, 0u)) return rc;
+        if (t_rand) return INERF_E_INVALID;
+    }
     if (n_rays == 0) return INERF_OK;              // an empty batch: its (possibly null) pointers are never touched
     if (!rays || !t_vals || !z_out || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
     const long long total = (long long)n_rays * n_samples;
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_sample_coarse, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rays, t_vals, t_rand,
-                       (long long)n_rays, n_samples, (flags & INERF_FLAG_LINDISP) ? 1 : 0, z_out);
+    if (drawn)
+        hipLaunchKernelGGL(k_sample_coarse<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rays, t_vals, t_rand,
+                           (long long)n_rays, n_samples, (flags & INERF_FLAG_LINDISP) ? 1 : 0, z_out, draw_params(*d, INERF_DRAW_STREAM_JITTER));
+    else
+        hipLaunchKernelGGL(k_sample_coarse<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rays, t_vals, t_rand,
+                           (long long)n_rays, n_samples, (flags & INERF_FLAG_LINDISP) ? 1 : 0, z_out, DrawParams{});
     return record(hipGetLastError());
 }
 
-extern "C" int inerf_composite(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
-                               const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim,
-                               uint32_t flags, const inerf_composite_out* out, void* stream) {
-    using namespace inerf;
+static unsigned noise_stream(const inerf_draw_args* d) {
+    return (d->flags & INERF_DRAW_FINE) ? INERF_DRAW_STREAM_NOISE_FINE : INERF_DRAW_STREAM_NOISE_COARSE;
+}
+
+static int composite_impl(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride, const float* noise,
+                          int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim, uint32_t flags,
+                          const inerf_composite_out* out, const inerf_draw_args* d, bool drawn, void* stream) {
     if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;    // a property of the shape: for an empty batch too, whatever the pointers
+    if (drawn) {
+        if (const int rc = draw_check(d, n_rays, INERF_DRAW_FINE)) return rc;
+        if (noise) return INERF_E_INVALID;
+    }
     if (n_rays == 0 && out) return INERF_OK;
     if (!raw || !z_vals || !rays_d || !out || n_rays < 0 || n_samples < 1 || rays_d_stride < 3) return INERF_E_INVALID;
     if (channels < INERF_BASE_CHANNELS || n_classes < 0 || feat_dim < 0 ||
@@ -498,56 +557,171 @@ extern "C" int inerf_composite(const float* raw, const float* z_vals, const floa
         return INERF_E_INVALID;
     const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_composite, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
-                       rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
-                       (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *out);
+    if (drawn)
+        hipLaunchKernelGGL(k_composite<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
+                           rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
+                           (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *out, draw_params(*d, noise_stream(d)));
+    else
+        hipLaunchKernelGGL(k_composite<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
+                           rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
+                           (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *out, DrawParams{});
     return record(hipGetLastError());
+}
+
+static int composite_backward_impl(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride, const float* noise,
+                                   int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim, uint32_t flags,
+                                   const inerf_composite_out* grads, float* d_raw, const inerf_draw_args* d, bool drawn, void* stream) {
+    if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;
+    if (drawn) {
+        if (const int rc = draw_check(d, n_rays, INERF_DRAW_FINE)) return rc;
+        if (noise) return INERF_E_INVALID;
+    }
+    if (n_rays == 0 && grads) return INERF_OK;
+    if (!raw || !z_vals || !rays_d || !grads || !d_raw || n_rays < 0 || n_samples < 1 || rays_d_stride < 3) return INERF_E_INVALID;
+    if (channels < INERF_BASE_CHANNELS + n_classes + feat_dim || n_classes < 0 || feat_dim < 0) return INERF_E_INVALID;
+    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
+    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
+    if (drawn)
+        hipLaunchKernelGGL(k_composite_bwd<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
+                           rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
+                           (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *grads, d_raw, draw_params(*d, noise_stream(d)));
+    else
+        hipLaunchKernelGGL(k_composite_bwd<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
+                           rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
+                           (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *grads, d_raw, DrawParams{});
+    return record(hipGetLastError());
+}
+
+static int sample_fine_impl(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int n_coarse, int n_importance,
+                            uint32_t flags, float* z_samples, float* z_merged, float* z_std, const inerf_draw_args* d, bool drawn,
+                            void* stream) {
+    // the limits are a property of the shape: they hold for an empty batch too, whatever the pointers
+    if (n_coarse < INERF_MIN_COARSE || n_coarse > kMaxCoarse || n_importance < 1 || n_importance > kMaxImportance) return INERF_E_UNSUPPORTED;
+    if (drawn) {
+        if (const int rc = draw_check(d, n_rays, 0u)) return rc;
+        if (u) return INERF_E_INVALID;
+    }
+    if (n_rays == 0) return INERF_OK;
+    if (!z_coarse || !weights || (!u && !drawn) || n_rays < 0) return INERF_E_INVALID;
+    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
+    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
+    if (drawn)
+        hipLaunchKernelGGL((k_sample_fine<false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z_coarse, weights, u,
+                           1, (long long)n_rays, n_coarse, n_importance, z_samples, z_merged, z_std, draw_params(*d, INERF_DRAW_STREAM_U));
+    else
+        hipLaunchKernelGGL((k_sample_fine<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z_coarse, weights, u,
+                           (flags & INERF_FLAG_U_PER_RAY) ? 1 : 0, (long long)n_rays, n_coarse, n_importance, z_samples,
+                           z_merged, z_std, DrawParams{});
+    return record(hipGetLastError());
+}
+
+static int sample_pdf_impl(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins, int n_samples,
+                           uint32_t flags, float* samples, const inerf_draw_args* d, bool drawn, void* stream) {
+    // (a [N, 0] weights tensor of a single bin edge has no storage: the size is what is wrong with it, not its null pointer)
+    if (n_bins < INERF_MIN_BINS || n_bins > kMaxCoarse || n_samples < 1 || n_samples > kMaxImportance) return INERF_E_UNSUPPORTED;
+    if (drawn) {
+        if (const int rc = draw_check(d, n_rays, 0u)) return rc;
+        if (u) return INERF_E_INVALID;
+    }
+    if (n_rays == 0) return INERF_OK;
+    if (!bins || !weights || (!u && !drawn) || !samples || n_rays < 0) return INERF_E_INVALID;
+    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
+    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
+    if (drawn)
+        hipLaunchKernelGGL((k_sample_fine<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bins, weights, u,
+                           1, (long long)n_rays, n_bins, n_samples, samples, (float*)nullptr, (float*)nullptr,
+                           draw_params(*d, INERF_DRAW_STREAM_U));
+    else
+        hipLaunchKernelGGL((k_sample_fine<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bins, weights, u,
+                           (flags & INERF_FLAG_U_PER_RAY) ? 1 : 0, (long long)n_rays, n_bins, n_samples, samples,
+                           (float*)nullptr, (float*)nullptr, DrawParams{});
+    return record(hipGetLastError());
+}
+
+}  // namespace inerf
+
+extern "C" int inerf_sample_coarse(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays,
+                                   int n_samples, uint32_t flags, float* z_out, void* stream) {
+    return inerf::sample_coarse_impl(rays, t_vals, t_rand, n_rays, n_samples, flags, z_out, nullptr, false, stream);
+}
+
+extern "C" int inerf_sample_coarse_drawn(const float* rays, const float* t_vals, const float* t_rand, int64_t n_rays,
+                                         int n_samples, uint32_t flags, float* z_out, const inerf_draw_args* draw, void* stream) {
+    return inerf::sample_coarse_impl(rays, t_vals, t_rand, n_rays, n_samples, flags, z_out, draw, true, stream);
+}
+
+extern "C" int inerf_composite(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
+                               const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim,
+                               uint32_t flags, const inerf_composite_out* out, void* stream) {
+    return inerf::composite_impl(raw, z_vals, rays_d, rays_d_stride, noise, n_rays, n_samples, channels, n_classes, feat_dim, flags, out,
+                                 nullptr, false, stream);
+}
+
+extern "C" int inerf_composite_drawn(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
+                                     const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes, int feat_dim,
+                                     uint32_t flags, const inerf_composite_out* out, const inerf_draw_args* draw, void* stream) {
+    return inerf::composite_impl(raw, z_vals, rays_d, rays_d_stride, noise, n_rays, n_samples, channels, n_classes, feat_dim, flags, out,
+                                 draw, true, stream);
 }
 
 extern "C" int inerf_composite_backward(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
                                         const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes,
                                         int feat_dim, uint32_t flags, const inerf_composite_out* grads, float* d_raw,
                                         void* stream) {
-    using namespace inerf;
-    if (n_samples > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0 && grads) return INERF_OK;
-    if (!raw || !z_vals || !rays_d || !grads || !d_raw || n_rays < 0 || n_samples < 1 || rays_d_stride < 3) return INERF_E_INVALID;
-    if (channels < INERF_BASE_CHANNELS + n_classes + feat_dim || n_classes < 0 || feat_dim < 0) return INERF_E_INVALID;
-    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
-    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_composite_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, z_vals, rays_d,
-                       rays_d_stride, noise, (long long)n_rays, n_samples, channels, n_classes, feat_dim,
-                       (flags & INERF_FLAG_WHITE_BKGD) ? 1 : 0, *grads, d_raw);
-    return record(hipGetLastError());
+    return inerf::composite_backward_impl(raw, z_vals, rays_d, rays_d_stride, noise, n_rays, n_samples, channels, n_classes, feat_dim,
+                                          flags, grads, d_raw, nullptr, false, stream);
+}
+
+extern "C" int inerf_composite_backward_drawn(const float* raw, const float* z_vals, const float* rays_d, int rays_d_stride,
+                                              const float* noise, int64_t n_rays, int n_samples, int channels, int n_classes,
+                                              int feat_dim, uint32_t flags, const inerf_composite_out* grads, float* d_raw,
+                                              const inerf_draw_args* draw, void* stream) {
+    return inerf::composite_backward_impl(raw, z_vals, rays_d, rays_d_stride, noise, n_rays, n_samples, channels, n_classes, feat_dim,
+                                          flags, grads, d_raw, draw, true, stream);
 }
 
 extern "C" int inerf_sample_fine(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int n_coarse,
                                  int n_importance, uint32_t flags, float* z_samples, float* z_merged, float* z_std,
                                  void* stream) {
+    return inerf::sample_fine_impl(z_coarse, weights, u, n_rays, n_coarse, n_importance, flags, z_samples, z_merged, z_std, nullptr, false,
+                                   stream);
+}
+
+extern "C" int inerf_sample_fine_drawn(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int n_coarse,
+                                       int n_importance, uint32_t flags, float* z_samples, float* z_merged, float* z_std,
+                                       const inerf_draw_args* draw, void* stream) {
+    return inerf::sample_fine_impl(z_coarse, weights, u, n_rays, n_coarse, n_importance, flags, z_samples, z_merged, z_std, draw, true,
+                                   stream);
+}
+
+extern "C" int inerf_sample_pdf(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins, int n_samples,
+                                uint32_t flags, float* samples, void* stream) {
+    return inerf::sample_pdf_impl(bins, weights, u, n_rays, n_bins, n_samples, flags, samples, nullptr, false, stream);
+}
+
+extern "C" int inerf_sample_pdf_drawn(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins, int n_samples,
+                                      uint32_t flags, float* samples, const inerf_draw_args* draw, void* stream) {
+    return inerf::sample_pdf_impl(bins, weights, u, n_rays, n_bins, n_samples, flags, samples, draw, true, stream);
+}
+
+extern "C" int inerf_draw_fill(const inerf_draw_args* draw, int stream_id, int64_t n_rays, int n_per_ray, float* out, void* stream) {
     using namespace inerf;
-    // the limits are a property of the shape: they hold for an empty batch too, whatever the pointers
-    if (n_coarse < INERF_MIN_COARSE || n_coarse > kMaxCoarse || n_importance < 1 || n_importance > kMaxImportance) return INERF_E_UNSUPPORTED;
+    if (n_per_ray > INERF_MAX_SAMPLES) return INERF_E_UNSUPPORTED;
+    if (const int rc = draw_check(draw, n_rays, 0u)) return rc;
+    if (stream_id < 0 || stream_id > 3 || n_per_ray < 1) return INERF_E_INVALID;
     if (n_rays == 0) return INERF_OK;
-    if (!z_coarse || !weights || !u || n_rays < 0) return INERF_E_INVALID;
-    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
-    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_sample_fine<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z_coarse, weights, u,
-                       (flags & INERF_FLAG_U_PER_RAY) ? 1 : 0, (long long)n_rays, n_coarse, n_importance, z_samples,
-                       z_merged, z_std);
+    if (!out) return INERF_E_INVALID;
+    const long long total = (long long)n_rays * n_per_ray;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_draw_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, (long long)n_rays, n_per_ray,
+                       draw_params(*draw, (unsigned)stream_id));
     return record(hipGetLastError());
 }
 
-extern "C" int inerf_sample_pdf(const float* bins, const float* weights, const float* u, int64_t n_rays, int n_bins,
-                                int n_samples, uint32_t flags, float* samples, void* stream) {
+extern "C" int inerf_draw_advance(int64_t* step_dev, void* stream) {
     using namespace inerf;
-    // (a [N, 0] weights tensor of a single bin edge has no storage: the size is what is wrong with it, not its null pointer)
-    if (n_bins < INERF_MIN_BINS || n_bins > kMaxCoarse || n_samples < 1 || n_samples > kMaxImportance) return INERF_E_UNSUPPORTED;
-    if (n_rays == 0) return INERF_OK;
-    if (!bins || !weights || !u || !samples || n_rays < 0) return INERF_E_INVALID;
-    const long long blocks = (n_rays + kRaysPerBlock - 1) / kRaysPerBlock;
-    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    hipLaunchKernelGGL(k_sample_fine<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bins, weights, u,
-                       (flags & INERF_FLAG_U_PER_RAY) ? 1 : 0, (long long)n_rays, n_bins, n_samples, samples,
-                       (float*)nullptr, (float*)nullptr);
+    if (!step_dev || (reinterpret_cast<uintptr_t>(step_dev) & 7u)) return INERF_E_INVALID;
+    hipLaunchKernelGGL(k_draw_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<long long*>(step_dev));
     return record(hipGetLastError());
 }

@@ -15,7 +15,9 @@ capturing stream, so they become kernel nodes like torch's own; nothing in the C
 read during capture; they are collected (kernels.captured_status) and read between the two graphs, so a batch that leaves
 f16's range never reaches the optimizer: it is re-run eagerly (where the front-end's own fallback evaluates it with torch
 layers) from the same RNG state.  Random draws inside the step (jitter, noise) use torch's graph-safe generator and advance
-on every replay.
+on every replay - or, when the step renders with a ``draws.DrawState`` (pass it as ``draws=`` here too), come from the kernels: the
+state's device-resident step counter is advanced by a captured launch, no generator is registered with the graph, and the eager
+re-run of a batch that left f16's range repeats the replay's draws (the counter is set back by one first).
 
 The ~115 small torch kernels above belong to a plain image loss; the reference's own loss (compute_intrinsic_loss on both levels,
 cluster MSE, cross-entropy) is ~300 more as torch expressions.  ``losses.object_step_loss`` / ``losses.ssr_step_loss`` are that loss
@@ -41,8 +43,8 @@ class GraphedTrainStep:
     The returned loss is a static tensor that the next call overwrites.
     """
 
-    def __init__(self, loss_fn, example_inputs, optimizer, warmup=2):
-        self.loss_fn, self.opt = loss_fn, optimizer
+    def __init__(self, loss_fn, example_inputs, optimizer, warmup=2, draws=None):
+        self.loss_fn, self.opt, self.draws = loss_fn, optimizer, draws
         self.static = [t.detach().clone() for t in example_inputs]
         dev = self.static[0].device
         for group in optimizer.param_groups:
@@ -66,6 +68,7 @@ class GraphedTrainStep:
         keep_s = {p: {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in optimizer.state[p].items()}
                   for p in self.params if p in optimizer.state and optimizer.state[p]}
         rng = torch.cuda.get_rng_state(dev)
+        draw_step = None if draws is None else draws.snapshot()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -82,6 +85,8 @@ class GraphedTrainStep:
                         else:
                             v.zero_()                      # a fresh optimizer: zeroed moments and step count ARE its initial state
         torch.cuda.set_rng_state(rng, dev)
+        if draws is not None:
+            draws.step_dev.copy_(draw_step)
         torch.cuda.synchronize(dev)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         saved, kernels.captured_status = kernels.captured_status, []
@@ -170,6 +175,8 @@ class GraphedTrainStep:
             # this batch left the split-precision kernels' range: its gradients are invalid and were NOT applied.  Same batch,
             # same random draws, eagerly - the front-end's own handler evaluates it with torch layers (object_level.render_rays).
             torch.cuda.set_rng_state(rng, dev)
+            if self.draws is not None:
+                self.draws.step_dev.sub_(1)               # the replay advanced it: the eager step draws what the replay drew
             self.fallbacks += 1
             loss = self._eager_step()                     # (re-binds every p.grad to a fresh eager tensor)
             self.loss.copy_(loss.detach())

@@ -51,16 +51,77 @@ def _new(like, *shape):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
-def sample_coarse(rays, t_vals, t_rand=None, lindisp=False):
-    """z_vals[N,S] (run_nerf.py:464-486 / trainer.py:730-746)."""
+# ---------------------------------------------------------------------------------------------------------------------
+# training draws (include/inerf.h, "Training draws"): a launcher's ``draw`` argument is an inerf_draw_args (_capi.DrawArgs, from
+# draws.DrawState.args) - the random tensor of the classic form is then drawn inside the kernel and must not be given
+# ---------------------------------------------------------------------------------------------------------------------
+def _draw_arg(draw, classic, name):
+    if draw is None:
+        return None
+    if not isinstance(draw, _capi.DrawArgs):
+        raise TypeError(f"draw must be an inerf_draw_args (DrawState.args()), got {type(draw).__name__}")
+    if classic is not None:
+        raise ValueError(f"{name} is drawn inside the kernel when draw is given: pass one or the other")
+    return C.byref(draw)
+
+
+def copy_draw(draw, **fields):
+    """A copy of an inerf_draw_args with ``fields`` replaced (the step tensor it reads stays referenced)."""
+    d = _capi.DrawArgs.from_buffer_copy(draw)
+    d.step_tensor = getattr(draw, "step_tensor", None)
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+def freeze_draw(draw):
+    """``draw`` reading an 8-byte device copy of its step counter (DrawState.snapshot): what a backward node keeps, so that it
+    regenerates the forward's draws even after the counter has advanced.  Capturable."""
+    t = getattr(draw, "step_tensor", None)
+    if t is None or not draw.step_dev:
+        return copy_draw(draw)
+    snap = t.clone()
+    d = copy_draw(draw, step_dev=snap.data_ptr())
+    d.step_tensor = snap
+    return d
+
+
+def draw_fill(draw, stream, n_rays, n_per_ray, device):
+    """One stream of the draws as the [n_rays, n_per_ray] tensor the classic entry points take (inerf_draw_fill)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"draw_fill on {device}: intrinsicnerf_amd runs only on a HIP device (no CPU / eager fallback exists)")
+    out = torch.empty((int(n_rays), int(n_per_ray)), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_draw_fill(_draw_arg(draw, None, ""), int(stream), int(n_rays), int(n_per_ray), _ptr(out), _stream(out))
+    _capi.check(rc, "inerf_draw_fill")
+    return out
+
+
+def draw_advance(step_dev):
+    """step_dev[0] += 1 on the device, as a launch of its own on the current stream (inerf_draw_advance)."""
+    if not (isinstance(step_dev, torch.Tensor) and step_dev.is_cuda and step_dev.dtype == torch.int64 and step_dev.numel() == 1):
+        raise ValueError("step_dev must be one int64 on a HIP device")
+    with torch.cuda.device(step_dev.device):
+        rc = _capi.lib().inerf_draw_advance(_ptr(step_dev), _stream(step_dev))
+    _capi.check(rc, "inerf_draw_advance")
+
+
+def sample_coarse(rays, t_vals, t_rand=None, lindisp=False, draw=None):
+    """z_vals[N,S] (run_nerf.py:464-486 / trainer.py:730-746).  ``draw``: the jitter is drawn in the kernel."""
     rays = _dev(rays, "rays", (None, RAY_FLOATS))
     t_vals = _dev(t_vals, "t_vals", (None,))
     n, s = rays.shape[0], t_vals.shape[0]
+    d = _draw_arg(draw, t_rand, "t_rand")
     t_rand = _opt(t_rand, "t_rand", (n, s), rays)
     z = _new(rays, n, s)
     with torch.cuda.device(rays.device):
-        rc = _capi.lib().inerf_sample_coarse(_ptr(rays), _ptr(t_vals), _ptr(t_rand), n, s,
-                                             FLAG_LINDISP if lindisp else 0, _ptr(z), _stream(rays))
+        if d is not None:
+            rc = _capi.lib().inerf_sample_coarse_drawn(_ptr(rays), _ptr(t_vals), None, n, s, FLAG_LINDISP if lindisp else 0, _ptr(z), d,
+                                                       _stream(rays))
+        else:
+            rc = _capi.lib().inerf_sample_coarse(_ptr(rays), _ptr(t_vals), _ptr(t_rand), n, s,
+                                                 FLAG_LINDISP if lindisp else 0, _ptr(z), _stream(rays))
     _capi.check(rc, "inerf_sample_coarse")
     return z
 
@@ -290,25 +351,28 @@ def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_col
 _COMPOSITE_KEYS = ("rgb", "disp", "acc", "depth", "albedo", "shading", "residual", "sem", "feat", "weights")
 
 
-def composite(raw, z_vals, rays_d, noise=None, white_bkgd=False, n_classes=0, feat_dim=0, want_weights=True):
+def composite(raw, z_vals, rays_d, noise=None, white_bkgd=False, n_classes=0, feat_dim=0, want_weights=True, draw=None):
     """raw2outputs (run_nerf.py:359-412 / model_utils.py:39-116) -> dict of maps.
 
     When ``raw`` requires grad (a training step through the staged path) the maps carry a grad_fn whose backward
     is the HIP kernel behind ``inerf_composite_backward``; ``z_vals`` / ``rays_d`` / ``noise`` get no gradient,
-    as in the reference (resampled depths are detached, run_nerf.py:501)."""
+    as in the reference (resampled depths are detached, run_nerf.py:501).  ``draw``: the noise is drawn in the kernel (scaled
+    by its noise_std; the fine pass's stream with its FINE flag) and the backward regenerates it from a snapshot of the step."""
+    _draw_arg(draw, noise, "noise")
     if torch.is_grad_enabled() and isinstance(raw, torch.Tensor) and raw.requires_grad:
-        keys, maps = _CompositeFn.run(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights)
+        keys, maps = _CompositeFn.run(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights, draw)
         return dict(zip(keys, maps))
-    return _composite_forward(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights)
+    return _composite_forward(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights, draw)
 
 
-def composite_backward(raw, z_vals, rays_d, grads, noise=None, white_bkgd=False, n_classes=0, feat_dim=0):
+def composite_backward(raw, z_vals, rays_d, grads, noise=None, white_bkgd=False, n_classes=0, feat_dim=0, draw=None):
     """d_raw[N,S,CH] for the output gradients in ``grads`` (dict: subset of rgb, disp, acc, depth, albedo, shading,
     residual, sem, feat, weights) - what autograd computes for raw2outputs in the reference's training step."""
     raw = _dev(raw, "raw", (None, None, None))
     n, s, ch = raw.shape
     z_vals = _dev(z_vals, "z_vals", (n, s))
     rays_d = _dev(rays_d, "rays_d", (n, 3))
+    d = _draw_arg(draw, noise, "noise")
     noise = _opt(noise, "noise", (n, s), raw)
     shapes = {"rgb": (n, 3), "albedo": (n, 3), "residual": (n, 3), "disp": (n,), "acc": (n,), "depth": (n,), "shading": (n,),
               "sem": (n, n_classes), "feat": (n, feat_dim), "weights": (n, s)}
@@ -321,9 +385,14 @@ def composite_backward(raw, z_vals, rays_d, grads, noise=None, white_bkgd=False,
     d_raw = _new(raw, n, s, ch)
     co = CompositeOut(**{k: t.data_ptr() for k, t in held.items()})
     with torch.cuda.device(raw.device):
-        rc = _capi.lib().inerf_composite_backward(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, _ptr(noise), n, s, ch, n_classes,
-                                                  feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), _ptr(d_raw),
-                                                  _stream(raw))
+        if d is not None:
+            rc = _capi.lib().inerf_composite_backward_drawn(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, None, n, s, ch, n_classes,
+                                                            feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), _ptr(d_raw),
+                                                            d, _stream(raw))
+        else:
+            rc = _capi.lib().inerf_composite_backward(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, _ptr(noise), n, s, ch, n_classes,
+                                                      feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), _ptr(d_raw),
+                                                      _stream(raw))
     _capi.check(rc, "inerf_composite_backward")
     return d_raw
 
@@ -332,17 +401,19 @@ class _CompositeFn(torch.autograd.Function):
     """Differentiable raw2outputs: HIP forward, HIP backward (the forward is recomputed there: only inputs are saved)."""
 
     @staticmethod
-    def run(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights):
+    def run(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, want_weights, draw=None):
         keys = [k for k in _COMPOSITE_KEYS if not (k == "sem" and n_classes == 0) and not (k == "feat" and feat_dim == 0)
                 and not (k == "weights" and not want_weights)]
-        maps = _CompositeFn.apply(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, tuple(keys))
+        maps = _CompositeFn.apply(raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, tuple(keys), draw)
         return keys, maps
 
     @staticmethod
-    def forward(ctx, raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, keys):
+    def forward(ctx, raw, z_vals, rays_d, noise, white_bkgd, n_classes, feat_dim, keys, draw=None):
         raw_c, z_c, d_c = raw.detach().float().contiguous(), z_vals.detach().float().contiguous(), rays_d.detach().float().contiguous()
         noise_c = None if noise is None else noise.detach().float().contiguous()
-        out = _composite_forward(raw_c, z_c, d_c, noise_c, white_bkgd, n_classes, feat_dim, "weights" in keys)
+        # drawn noise is not kept: the node holds the draw arguments with an 8-byte copy of the step they were drawn at
+        ctx.draw = None if draw is None else freeze_draw(draw)
+        out = _composite_forward(raw_c, z_c, d_c, noise_c, white_bkgd, n_classes, feat_dim, "weights" in keys, ctx.draw)
         # Outputs the loss does not use must arrive as None, not as zero tensors: the reference's autograd never visits the
         # branch of an unused output, while a ZERO cotangent on disp = 1 / (depth / acc) turns into NaN on every ray with
         # acc == 0 (0 x d(1/(0/0))) - and a trained network has such rays (sigma <= 0 along a ray through empty space) in every
@@ -359,15 +430,16 @@ class _CompositeFn(torch.autograd.Function):
         raw, z_vals, rays_d = saved[:3]
         noise = saved[3] if has_noise else None
         grads = {k: g for k, g in zip(keys, gouts) if g is not None}
-        d_raw = composite_backward(raw, z_vals, rays_d, grads, noise, white_bkgd, n_classes, feat_dim)
-        return d_raw, None, None, None, None, None, None, None
+        d_raw = composite_backward(raw, z_vals, rays_d, grads, noise, white_bkgd, n_classes, feat_dim, ctx.draw)
+        return d_raw, None, None, None, None, None, None, None, None
 
 
-def _composite_forward(raw, z_vals, rays_d, noise=None, white_bkgd=False, n_classes=0, feat_dim=0, want_weights=True):
+def _composite_forward(raw, z_vals, rays_d, noise=None, white_bkgd=False, n_classes=0, feat_dim=0, want_weights=True, draw=None):
     raw = _dev(raw, "raw", (None, None, None))
     n, s, ch = raw.shape
     z_vals = _dev(z_vals, "z_vals", (n, s))
     rays_d = _dev(rays_d, "rays_d", (n, 3))
+    d = _draw_arg(draw, noise, "noise")
     noise = _opt(noise, "noise", (n, s), raw)
     out = {k: _new(raw, n, 3) for k in ("rgb", "albedo", "residual")}
     out.update({k: _new(raw, n) for k in ("disp", "acc", "depth", "shading")})
@@ -379,8 +451,12 @@ def _composite_forward(raw, z_vals, rays_d, noise=None, white_bkgd=False, n_clas
         out["weights"] = _new(raw, n, s)
     co = CompositeOut(**{k: t.data_ptr() for k, t in out.items()})
     with torch.cuda.device(raw.device):
-        rc = _capi.lib().inerf_composite(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, _ptr(noise), n, s, ch, n_classes,
-                                         feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), _stream(raw))
+        if d is not None:
+            rc = _capi.lib().inerf_composite_drawn(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, None, n, s, ch, n_classes,
+                                                   feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), d, _stream(raw))
+        else:
+            rc = _capi.lib().inerf_composite(_ptr(raw), _ptr(z_vals), _ptr(rays_d), 3, _ptr(noise), n, s, ch, n_classes,
+                                             feat_dim, FLAG_WHITE_BKGD if white_bkgd else 0, C.byref(co), _stream(raw))
     _capi.check(rc, "inerf_composite")
     return out
 
@@ -394,30 +470,42 @@ def _u_arg(u, n, n_imp, like):
     raise ValueError(f"u has shape {tuple(u.shape)}, expected ({n_imp},) or ({n}, {n_imp})")
 
 
-def sample_fine(z_coarse, weights, u, n_importance):
-    """z_mid + sample_pdf + sort(cat) + std (run_nerf.py:499-503,519) -> (z_samples, z_merged, z_std)."""
+def sample_fine(z_coarse, weights, u, n_importance, draw=None):
+    """z_mid + sample_pdf + sort(cat) + std (run_nerf.py:499-503,519) -> (z_samples, z_merged, z_std).  ``draw``: per-ray u drawn in
+    the kernel (``u`` None)."""
     z_coarse = _dev(z_coarse, "z_coarse", (None, None))
     n, sc = z_coarse.shape
     weights = _dev(weights, "weights", (n, sc))
-    u, flags = _u_arg(u, n, n_importance, z_coarse)
+    d = _draw_arg(draw, u, "u")
+    if d is None:
+        u, flags = _u_arg(u, n, n_importance, z_coarse)
     z_s, z_m, z_std = _new(z_coarse, n, n_importance), _new(z_coarse, n, sc + n_importance), _new(z_coarse, n)
     with torch.cuda.device(z_coarse.device):
-        rc = _capi.lib().inerf_sample_fine(_ptr(z_coarse), _ptr(weights), _ptr(u), n, sc, n_importance, flags,
-                                           _ptr(z_s), _ptr(z_m), _ptr(z_std), _stream(z_coarse))
+        if d is not None:
+            rc = _capi.lib().inerf_sample_fine_drawn(_ptr(z_coarse), _ptr(weights), None, n, sc, n_importance, 0,
+                                                     _ptr(z_s), _ptr(z_m), _ptr(z_std), d, _stream(z_coarse))
+        else:
+            rc = _capi.lib().inerf_sample_fine(_ptr(z_coarse), _ptr(weights), _ptr(u), n, sc, n_importance, flags,
+                                               _ptr(z_s), _ptr(z_m), _ptr(z_std), _stream(z_coarse))
     _capi.check(rc, "inerf_sample_fine")
     return z_s, z_m, z_std
 
 
-def sample_pdf(bins, weights, u, n_samples):
-    """Stand-alone sample_pdf(bins, weights, N) (run_nerf_helpers.py:402-445)."""
+def sample_pdf(bins, weights, u, n_samples, draw=None):
+    """Stand-alone sample_pdf(bins, weights, N) (run_nerf_helpers.py:402-445).  ``draw``: per-ray u drawn in the kernel (``u`` None)."""
     bins = _dev(bins, "bins", (None, None))
     n, nb = bins.shape
     weights = _dev(weights, "weights", (n, nb - 1))
-    u, flags = _u_arg(u, n, n_samples, bins)
+    d = _draw_arg(draw, u, "u")
+    if d is None:
+        u, flags = _u_arg(u, n, n_samples, bins)
     out = _new(bins, n, n_samples)
     with torch.cuda.device(bins.device):
-        rc = _capi.lib().inerf_sample_pdf(_ptr(bins), _ptr(weights), _ptr(u), n, nb, n_samples, flags, _ptr(out),
-                                          _stream(bins))
+        if d is not None:
+            rc = _capi.lib().inerf_sample_pdf_drawn(_ptr(bins), _ptr(weights), None, n, nb, n_samples, 0, _ptr(out), d, _stream(bins))
+        else:
+            rc = _capi.lib().inerf_sample_pdf(_ptr(bins), _ptr(weights), _ptr(u), n, nb, n_samples, flags, _ptr(out),
+                                              _stream(bins))
     _capi.check(rc, "inerf_sample_pdf")
     return out
 
@@ -427,8 +515,10 @@ _MAP_KEYS = ("rgb", "disp", "acc", "depth", "albedo", "shading", "residual")
 
 def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_importance, t_vals, u=None, t_rand=None,
                       noise_coarse=None, noise_fine=None, white_bkgd=False, lindisp=False, endpoint=False,
-                      want_raw_coarse=False, want_raw_fine=False, want_stages=False, want_sem=True):
-    """Whole render_rays path for one ray batch through ``inerf_render_rays``.
+                      want_raw_coarse=False, want_raw_fine=False, want_stages=False, want_sem=True, draw=None):
+    """Whole render_rays path for one ray batch through ``inerf_render_rays`` - or, with ``draw`` (an inerf_draw_args whose PERTURB
+    flag and noise_std say what the reference would draw), through ``inerf_render_rays_drawn``: t_rand and the noise tensors must
+    then be None, and u too when PERTURB is set.
 
     Returns a dict with ``{rgb,disp,acc,depth,albedo,shading,residual[,sem]}_{coarse,fine}``, ``z_std``
     and, on request, ``raw_*`` / stage tensors (``z_coarse, weights_coarse, z_samples, z_fine,
@@ -442,12 +532,16 @@ def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_impor
     packed_coarse = _dev(packed_coarse, "packed_coarse", (None,))
     packed_fine = _opt(packed_fine, "packed_fine", (None,), rays)
     t_vals = _dev(t_vals, "t_vals", (n_samples,))
+    d = _draw_arg(draw, next((t for t in (t_rand, noise_coarse, noise_fine) if t is not None), None), "t_rand / noise")
+    drawn_u = d is not None and bool(draw.flags & _capi.DRAW_PERTURB)
+    if drawn_u and u is not None:
+        raise ValueError("u is drawn inside the kernel when draw has the PERTURB flag: pass one or the other")
     t_rand = _opt(t_rand, "t_rand", (n, n_samples), rays)
     noise_coarse = _opt(noise_coarse, "noise_coarse", (n, n_samples), rays)
     s_f = n_samples + n_importance
     noise_fine = _opt(noise_fine, "noise_fine", (n, s_f), rays) if n_importance > 0 else None
     flags = (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) | (FLAG_ENDPOINT if endpoint else 0)
-    if n_importance > 0:
+    if n_importance > 0 and not drawn_u:
         if u is None:
             raise ValueError("u is required when n_importance > 0")
         u, uf = _u_arg(u, n, n_importance, rays)
@@ -476,7 +570,7 @@ def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_impor
     args.rays, args.n_rays, args.n_samples, args.n_importance, args.flags = rays.data_ptr(), n, n_samples, n_importance, flags
     args.t_vals = t_vals.data_ptr()
     args.t_rand = t_rand.data_ptr() if t_rand is not None else None
-    args.u = u.data_ptr() if n_importance > 0 else None
+    args.u = u.data_ptr() if (n_importance > 0 and not drawn_u) else None
     args.noise_coarse = noise_coarse.data_ptr() if noise_coarse is not None else None
     args.noise_fine = noise_fine.data_ptr() if noise_fine is not None else None
     args.coarse = maps("coarse", n_samples, False)
@@ -508,7 +602,7 @@ def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_impor
         args.status = out["status"].data_ptr()
         args.status_rays = _status_rays if words > 1 else 0
     with torch.cuda.device(rays.device):
-        rc = L.inerf_render_rays(C.byref(args), _stream(rays))
+        rc = L.inerf_render_rays(C.byref(args), _stream(rays)) if d is None else L.inerf_render_rays_drawn(C.byref(args), d, _stream(rays))
     _capi.check(rc, "inerf_render_rays")
     # `ws` and the input tensors are kept alive by the caching allocator's stream semantics: they are
     # released on the same stream the kernels were enqueued on.

@@ -42,6 +42,13 @@ trainers' ``optimizer.zero_grad()``, ``optimizer.step()``, learning-rate decay a
 is inline in ``train()`` (run_nerf.py:886-938) and cannot be rebound from outside: for ``run_nerf.py`` the flag only says so, once;
 INTEGRATION.md has its three-line replacement by ``batches.ObjectBatcher.next(i)``.
 
+``--inerf-draws`` (opt-in) draws the training step's random tensors - the stratified jitter, the density noise of both passes and
+the inverse-CDF variates - inside the kernels (csrc/draws.h, ``draws.DrawState``) instead of with ``torch.rand`` / ``torch.randn``:
+``create_nerf`` in ``run_nerf.py``'s namespace is wrapped so that ``render_kwargs_train["draws"]`` holds a ``DrawState``, and
+``SSRTrainer.draws`` yields one per trainer.  Both are created on first use with ``seed = torch.initial_seed()``, i.e. after the script's
+own seeding.  The draws are this package's counter-based ones, not torch's streams: a seeded run is reproducible, and its renders do
+not depend on ``chunk``.  Without the flag nothing of this is bound.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -127,7 +134,37 @@ def _with_inerf_adam_ssr(create_ssr):
     return create_ssr_inerf_adam
 
 
-def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False):
+def _with_inerf_draws_nerf(create_nerf):
+    """``create_nerf`` whose ``render_kwargs_train`` (first return value, run_nerf.py:356) carries ``draws``: a DrawState seeded with
+    ``torch.initial_seed()`` on the device of the networks' parameters."""
+    import functools
+
+    @functools.wraps(create_nerf)
+    def create_nerf_inerf_draws(*args, **kwargs):
+        import torch
+        from . import draws
+        out = list(create_nerf(*args, **kwargs))
+        params = list(out[0]["network_fn"].parameters())
+        out[0]["draws"] = draws.DrawState(torch.initial_seed(), params[0].device)
+        return tuple(out)
+    return create_nerf_inerf_draws
+
+
+class _TrainerDraws:
+    """``SSRTrainer.draws``: one DrawState per trainer, created when the render path first asks for it (the networks exist then and
+    the script has seeded torch), seed = ``torch.initial_seed()``."""
+
+    def __get__(self, obj, owner=None):
+        if obj is None:
+            return self
+        import torch
+        from . import draws
+        state = draws.DrawState(torch.initial_seed(), next(obj.ssr_net_coarse.parameters()).device)
+        obj.__dict__["draws"] = state                  # (a non-data descriptor: the instance attribute wins from now on)
+        return state
+
+
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
     names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ()) + ((LOSS_SYMBOL,) if losses else ())
@@ -136,6 +173,10 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     if adam:
         namespace["create_nerf"] = _with_inerf_adam_nerf(namespace["create_nerf"])
         names = names + ("create_nerf",)
+    if draws:
+        namespace["create_nerf"] = _with_inerf_draws_nerf(namespace["create_nerf"])
+        if "create_nerf" not in names:
+            names = names + ("create_nerf",)
     if cluster_fit:
         rebind_cluster_fit("cluster")                  # run_nerf.py:24 `from cluster import Cluster, Cluster_Manager`
     if with_render_path and "Cluster_Manager" in namespace:
@@ -148,7 +189,7 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     bound = {}
@@ -156,7 +197,7 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
     methods = SSR_METHODS + (("render_path",) if with_render_path else ())
     for name in methods:
         setattr(trainer.SSRTrainer, name, getattr(ssr.SSRRenderMixin, name))
-    for extra in ("return_raw", "check_numerics", "_staged"):          # what the mixin's methods read besides the trainer's attributes
+    for extra in ("return_raw", "check_numerics", "_staged", "draws"):          # what the mixin's methods read besides the trainer's attributes
         setattr(trainer.SSRTrainer, extra, getattr(ssr.SSRRenderMixin, extra))
     if with_render_path and hasattr(trainer, "Cluster_Manager"):
         # trainer.py:1065 renders with update_cluster = not self.no_cluster: the fitting is the reference's class (trainer.py:16, :1416-1418)
@@ -187,6 +228,9 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
     if batches:                                        # trainer.py:627-691; its draws stay SSR.models.rays.sampling_index
         trainer.SSRTrainer.sample_data = ssr.SSRRenderMixin.sample_data
         bound["SSR.training.trainer.SSRTrainer"].append("sample_data")
+    if draws:                                          # (without the flag SSRTrainer.draws is the mixin's default, None)
+        trainer.SSRTrainer.draws = _TrainerDraws()
+        bound["SSR.training.trainer.SSRTrainer"].append("draws")
     return bound
 
 
@@ -202,7 +246,7 @@ def _object_batches_notice():
         _told_object_batches = True
 
 
-def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False):
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -216,12 +260,12 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws)
         if batches:
             _object_batches_notice()
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws)
     return mod, main
 
 
@@ -242,6 +286,9 @@ def main(argv=None):
     batches = "--inerf-batches" in argv
     if batches:
         argv.remove("--inerf-batches")
+    draws = "--inerf-draws" in argv
+    if draws:
+        argv.remove("--inerf-draws")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -252,6 +299,8 @@ def main(argv=None):
     extra = dict(adam=True) if adam else {}            # (by keyword and only when given, for the same reason)
     if batches:
         extra["batches"] = True
+    if draws:
+        extra["draws"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

@@ -325,11 +325,24 @@ _RET_0 = (("rgb0", "rgb"), ("disp0", "disp"), ("acc0", "acc"), ("albedo0", "albe
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
-                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False):
-    """Volumetric rendering of one ray batch - run_nerf.py:415-528 (same dict keys, same RNG draw order)."""
+                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, draws=None,
+                ray_base=None):
+    """Volumetric rendering of one ray batch - run_nerf.py:415-528 (same dict keys, same RNG draw order).
+
+    ``draws`` (a ``draws.DrawState``; default None = torch's generator, as before): whatever the reference draws - the jitter and the
+    per-ray u when ``perturb > 0``, the density noise when ``raw_noise_std > 0`` - is drawn inside the kernels as a function of
+    (seed, step, stream, ``ray_base`` + ray, sample), so the result does not depend on how the rays were chunked.  ``ray_base``: global
+    index of this batch's first ray - given by a chunk loop, which then also advances the step; None: this call is the whole
+    batch (base 0) and advances the step itself.  A call that draws nothing (``perturb == 0`` and ``raw_noise_std == 0``) leaves the step
+    alone: the step counts drawing renders, so eval renders between training steps do not shift the training draws."""
     ray_batch = ray_batch.float()
     n = ray_batch.shape[0]
     dev = ray_batch.device
+    if draws is not None and pytest:
+        raise ValueError("render_rays: pytest=True replaces the random tensors by numpy's; it cannot be combined with draws")
+    drawn_perturb = draws is not None and perturb > 0.
+    drawn_noise = draws is not None and raw_noise_std > 0.
+    base = 0 if ray_base is None else int(ray_base)
     if ray_batch.shape[-1] <= 8:
         raise NotImplementedError("render_rays without view directions: the 11-channel intrinsic network needs "
                                   "use_viewdirs=True (run_nerf_helpers.py:281-282 is unused by every config)")
@@ -342,14 +355,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     # random inputs, drawn in the reference's order: t_rand (:478), coarse noise (:387), u (helpers:414), fine noise
     t_vals = torch.linspace(0., 1., steps=N_samples, device=dev)
     t_rand = None
-    if perturb > 0.:
+    if perturb > 0. and not drawn_perturb:
         t_rand = torch.rand(n, N_samples, device=dev)
         if pytest:
             np.random.seed(0)
             t_rand = torch.Tensor(np.random.rand(n, N_samples)).to(dev)
 
     def noise(s):
-        if not raw_noise_std > 0.:
+        if not raw_noise_std > 0. or drawn_noise:
             return None
         nz = torch.randn(n, s, device=dev) * raw_noise_std
         if pytest:
@@ -363,17 +376,20 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         train_desc, desc = _train_desc(desc), None
     if desc is not None:
         noise_c = noise(N_samples)
-        u = _draw_u(n, N_importance, perturb == 0., pytest, dev) if N_importance > 0 else None
+        u = _draw_u(n, N_importance, perturb == 0., pytest, dev) if (N_importance > 0 and not drawn_perturb) else None
         noise_f = noise(N_samples + N_importance) if N_importance > 0 else None
         fine_net = network_fine if network_fine is not None else network_fn
+        draw = draws.args(base, raw_noise_std if drawn_noise else 0., perturb=True if drawn_perturb else False) if (
+            drawn_perturb or drawn_noise) else None
 
         def run(d):
             res = kernels.render_rays_fused(
                 d, packing.packed_for_module(network_fn, d, dev),
                 packing.packed_for_module(fine_net, d, dev) if N_importance > 0 else None,
                 ray_batch, N_samples, N_importance, t_vals, u, t_rand, noise_c, noise_f, white_bkgd, lindisp,
-                want_raw_coarse=retraw and N_importance == 0, want_raw_fine=retraw)
-            # eval-mode chunks of a frame (no RNG draws to repeat) leave the check to batchify_rays' end-of-frame one
+                want_raw_coarse=retraw and N_importance == 0, want_raw_fine=retraw, draw=draw)
+            # eval-mode chunks of a frame (no RNG draws to repeat) leave the check to batchify_rays' end-of-frame one; so do chunks
+            # whose draws come from the kernels (a second render of the chunk repeats them: the step has not advanced)
             kernels.check_f16_range(res.pop("status", None), "render_rays", deferrable=t_rand is None and noise_c is None)
             return res
 
@@ -404,16 +420,19 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                         raw = network_query_fn(pts, viewdirs, fn)
                 return raw
 
-            z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, lindisp)
+            z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, lindisp, draw=draws.args(base) if drawn_perturb else None)
             raw = query(z_vals, network_fn)
-            c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples), white_bkgd)
+            c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples), white_bkgd,
+                                  draw=draws.args(base, raw_noise_std) if drawn_noise else None)
             ret = {rk: c[ok] for rk, ok in _RET_MAP}
             if N_importance > 0:
                 c0 = c
-                u = _draw_u(n, N_importance, perturb == 0., pytest, dev)
-                z_samples, z_vals, z_std = kernels.sample_fine(z_vals, c0["weights"], u, N_importance)
+                u = None if drawn_perturb else _draw_u(n, N_importance, perturb == 0., pytest, dev)
+                z_samples, z_vals, z_std = kernels.sample_fine(z_vals, c0["weights"], u, N_importance,
+                                                               draw=draws.args(base) if drawn_perturb else None)
                 raw = query(z_vals, network_fn if network_fine is None else network_fine)
-                c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples + N_importance), white_bkgd)
+                c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples + N_importance), white_bkgd,
+                                      draw=draws.args(base, raw_noise_std, fine=True) if drawn_noise else None)
                 ret = {rk: c[ok] for rk, ok in _RET_MAP}
                 for rk, ok in _RET_0:
                     ret[rk] = c0[ok]
@@ -429,7 +448,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             # after each network leaves the GPU idle while the host prepares the next launches).  If it trips, the whole batch
             # is evaluated again layer by layer in exact fp32 (layered.evaluate: HIP forward and backward, no range limit) - with
             # the random draws repeated, so it consumes the RNG like the reference would.
-            redraw = (raw_noise_std > 0. or (perturb > 0. and N_importance > 0)) and not kernels._capturing()
+            redraw = ((raw_noise_std > 0. and not drawn_noise) or (perturb > 0. and N_importance > 0 and not drawn_perturb)) and not kernels._capturing()
             rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None) if redraw else None
             np_state = np.random.get_state() if pytest else None
             try:
@@ -449,6 +468,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         for k in ret:
             if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
                 print(f"! [Numerical Error] {k} contains nan or inf.")
+    if (drawn_perturb or drawn_noise) and ray_base is None:      # the whole batch was this one call: the next call draws at the next step
+        draws.advance()
     return ret
 
 
@@ -476,6 +497,22 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     (kernels.deferred_range_checks): a frame is one host synchronisation, not one per chunk.  Chunks whose word reports an
     out-of-range activation - and only those - are rendered again with the exact fp32 kernel (only eval-mode chunks defer,
     so no random draw is repeated; chunks that draw random numbers check and fall back inside render_rays)."""
+    draws = kwargs.get("draws")
+    if draws is not None and (kwargs.get("perturb", 0.) > 0. or kwargs.get("raw_noise_std", 0.) > 0.):
+        # every chunk draws at the same step with its first global ray index as base (the result does not depend on `chunk`); the step
+        # advances once, after the last chunk - a chunk rendered again in exact fp32 below repeats its own draws
+        # (a caller that renders a band of a larger batch passes the band's start as ray_base)
+        try:
+            return _batchify_rays(rays_flat, chunk, kwargs)
+        finally:
+            draws.advance()
+    return _batchify_rays(rays_flat, chunk, kwargs)
+
+
+def _batchify_rays(rays_flat, chunk, kwargs):
+    kwargs = dict(kwargs)
+    base0 = int(kwargs.pop("ray_base", None) or 0)
+    based = (lambda i: {"ray_base": base0 + i}) if kwargs.get("draws") is not None else (lambda i: {})
     big = _coalesced(rays_flat, chunk, kwargs)
     if big > chunk:
         # eval mode, fused networks, no raw: nothing depends on the chunk boundaries (results are bit-identical for any chunking), so
@@ -485,7 +522,7 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         with kernels.deferred_range_checks("render", raise_on_trip=False) as block, kernels.chunked_status(chunk):
             for j, i in enumerate(range(0, rays_flat.shape[0], big)):
                 block.tag = j
-                rets.append(render_rays(rays_flat[i:i + big], **kwargs))
+                rets.append(render_rays(rays_flat[i:i + big], **kwargs, **based(i)))
         out = {k: (rets[0][k] if len(rets) == 1 else torch.cat([r[k] for r in rets], 0)) for k in rets[0]}
         if block.tripped:
             # tags: (piece, word) of a piece with one word per caller's chunk, or the piece itself (it held no more than one chunk)
@@ -494,7 +531,7 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
                                       "split-precision MLP kernel.")
             with _capi.forced_precision(_capi.PREC_F32):
                 for i, n_i in spans:
-                    again = render_rays(rays_flat[i:i + n_i], **kwargs)
+                    again = render_rays(rays_flat[i:i + n_i], **kwargs, **based(i))
                     for k in out:
                         out[k][i:i + n_i] = again[k]
         return out
@@ -503,13 +540,13 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     with kernels.deferred_range_checks("render", raise_on_trip=False) as block:
         for j, i in enumerate(starts):
             block.tag = j
-            rets.append(render_rays(rays_flat[i:i + chunk], **kwargs))
+            rets.append(render_rays(rays_flat[i:i + chunk], **kwargs, **based(i)))
     if block.tripped:
         kernels.warn_f32_fallback(f"render: {len(block.tripped)} of {len(starts)} chunks left the f16 range of the split-precision "
                                   "MLP kernel.")
         with _capi.forced_precision(_capi.PREC_F32):
             for j in block.tripped:
-                rets[j] = render_rays(rays_flat[starts[j]:starts[j] + chunk], **kwargs)
+                rets[j] = render_rays(rays_flat[starts[j]:starts[j] + chunk], **kwargs, **based(starts[j]))
     if not rets:
         return {}
     return {k: (rets[0][k] if len(rets) == 1 else torch.cat([r[k] for r in rets], 0)) for k in rets[0]}

@@ -247,18 +247,22 @@ def create_rays(num_rays, Ts_c2w, height, width, fx, fy, cx, cy, near, far, c2w_
     return rays
 
 
-def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None):
+def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None, with_ray_base=False):
     """training_utils.py:5-17.  As in object_level.batchify_rays the chunks' f16 range words are read together after the
     last chunk (one host synchronisation per frame) and only the chunks that left the range are rendered again in exact
     fp32.  ``coalesce_to`` (SSRRenderMixin.render_rays, eval-mode frames whose result cannot depend on the chunk boundaries):
     rays per call instead of ``chunk``; the launches keep one f16 range word per ``chunk`` rays, so a chunk that leaves the range is still the
-    only one rendered again."""
+    only one rendered again.  ``with_ray_base``: ``render_fn`` is also given every chunk's first global ray index (``ray_base=``), the base
+    of its training draws (SSRRenderMixin.draws)."""
+    def piece(i, count):
+        return render_fn(rays_flat[i:i + count], ray_base=i) if with_ray_base else render_fn(rays_flat[i:i + count])
+
     if coalesce_to is not None and coalesce_to > chunk:
         rets = []
         with kernels.deferred_range_checks("render_rays", raise_on_trip=False) as block, kernels.chunked_status(chunk):
             for j, i in enumerate(range(0, rays_flat.shape[0], coalesce_to)):
                 block.tag = j
-                rets.append(render_fn(rays_flat[i:i + coalesce_to]))
+                rets.append(piece(i, coalesce_to))
         out = {k: torch.cat([r[k] for r in rets], 0) for k in rets[0]}
         if block.tripped:     # one range word per caller's chunk (kernels.chunked_status): only the chunks that left the range, in exact fp32
             spans = sorted({(t[0] * coalesce_to + t[1] * chunk, chunk) if isinstance(t, tuple) else (t * coalesce_to, coalesce_to)
@@ -267,7 +271,7 @@ def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None):
                                       "split-precision MLP kernel.")
             with _capi.forced_precision(_capi.PREC_F32):
                 for i, n_i in spans:
-                    again = render_fn(rays_flat[i:i + n_i])
+                    again = piece(i, n_i)
                     for k in out:
                         out[k][i:i + n_i] = again[k]
         return out
@@ -276,13 +280,13 @@ def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None):
     with kernels.deferred_range_checks("render_rays", raise_on_trip=False) as block:
         for j, i in enumerate(starts):
             block.tag = j
-            rets.append(render_fn(rays_flat[i:i + chunk]))
+            rets.append(piece(i, chunk))
     if block.tripped:
         kernels.warn_f32_fallback(f"render_rays: {len(block.tripped)} of {len(starts)} chunks left the f16 range of the "
                                   "split-precision MLP kernel.")
         with _capi.forced_precision(_capi.PREC_F32):
             for j in block.tripped:
-                rets[j] = render_fn(rays_flat[starts[j]:starts[j] + chunk])
+                rets[j] = piece(starts[j], chunk)
     if not rets:
         return {}
     return {k: torch.cat([r[k] for r in rets], 0) for k in rets[0]}
@@ -304,10 +308,23 @@ class SSRRenderMixin:
 
     return_raw = True
     check_numerics = True
+    # a draws.DrawState: in training mode the jitter, the per-ray u (perturb > 0) and the density noise (raw_noise_std > 0) are drawn inside
+    # the kernels as a function of (seed, step, stream, global ray index, sample) - the same bits for any `chunk`; None: torch's generator
+    draws = None
 
     def render_rays(self, flat_rays):
         ray_shape = flat_rays.shape
-        all_ret = batchify_rays(self.volumetric_rendering, flat_rays, self.chunk, self._coalesced(flat_rays))      # one host synchronisation per frame
+        draws = self.draws
+        if draws is not None and bool(self.training) and (self.perturb > 0. or self.raw_noise_std > 0.):
+            # (eval-mode frames and renders that draw nothing leave the step alone: it counts drawing renders) every chunk draws at the same step, based at its first global ray index; the step advances once, after the last chunk (a
+            # chunk rendered again in exact fp32 repeats its own draws)
+            try:
+                all_ret = batchify_rays(self.volumetric_rendering, flat_rays, self.chunk,
+                                        self._coalesced(flat_rays), with_ray_base=True)
+            finally:
+                draws.advance()
+        else:
+            all_ret = batchify_rays(self.volumetric_rendering, flat_rays, self.chunk, self._coalesced(flat_rays))      # one host synchronisation per frame
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], list(ray_shape[:-1]) + list(all_ret[k].shape[1:]))
         return all_ret
@@ -436,9 +453,12 @@ class SSRRenderMixin:
         channels = _capi.BASE_CHANNELS + c + (_capi.ENDPOINT_DIM if (self.endpoint_feat and self.N_importance > 0) else 0)
         return kernels.coalesced_chunk(flat_rays.shape[0], self.chunk, self.N_samples, self.N_importance, channels, flat_rays.device)
 
-    def volumetric_rendering(self, ray_batch):
+    def volumetric_rendering(self, ray_batch, ray_base=None):
+        """trainer.py:717-808 for one ray batch.  With ``self.draws``: ``ray_base`` is the global index of the batch's first ray (given
+        by render_rays' chunk loop, which advances the step); None: this call is the whole batch (base 0) and advances the step itself."""
         ray_batch = ray_batch.float()
         n, dev = ray_batch.shape[0], ray_batch.device
+        draws, base = self.draws, 0 if ray_base is None else int(ray_base)
         if ray_batch.shape[-1] <= 8:
             raise NotImplementedError("volumetric_rendering needs view directions (use_viewdirs: true in every config)")
         desc = _fusable(self.ssr_net_coarse, self.embed_fn, self.embeddirs_fn)
@@ -453,16 +473,26 @@ class SSRRenderMixin:
         training = bool(self.training)
         t_vals = torch.linspace(0., 1., steps=self.N_samples, device=dev)
         # RNG draws in the reference's order: t_rand (:744), coarse noise (model_utils.py:70), u (rays.py:197), fine noise
-        t_rand = torch.rand(n, self.N_samples, device=dev) if (self.perturb > 0. and training) else None
         std = self.raw_noise_std if training else 0
-        noise_c = torch.randn(n, self.N_samples, device=dev) * std if std > 0. else None
+        drawn_perturb = draws is not None and self.perturb > 0. and training
+        drawn_noise = draws is not None and std > 0.
+        t_rand = torch.rand(n, self.N_samples, device=dev) if (self.perturb > 0. and training and not drawn_perturb) else None
+        noise_c = torch.randn(n, self.N_samples, device=dev) * std if (std > 0. and not drawn_noise) else None
         u = noise_f = None
         if self.N_importance > 0:
             det = (self.perturb == 0.) or (not training)
-            u = (torch.linspace(0., 1., steps=self.N_importance, device=dev) if det
-                 else torch.rand(n, self.N_importance, device=dev))
-            noise_f = torch.randn(n, self.N_samples + self.N_importance, device=dev) * std if std > 0. else None
+            if not drawn_perturb:
+                u = (torch.linspace(0., 1., steps=self.N_importance, device=dev) if det
+                     else torch.rand(n, self.N_importance, device=dev))
+            noise_f = torch.randn(n, self.N_samples + self.N_importance, device=dev) * std if (std > 0. and not drawn_noise) else None
         ep = bool(self.endpoint_feat) and self.N_importance > 0
+        # the drawn forms: (jitter / u, coarse noise, fine noise) for the staged path, one inerf_draw_args for the fused one
+        dr = None
+        if drawn_perturb or drawn_noise:
+            dr = {"perturb": draws.args(base) if drawn_perturb else None,
+                  "noise_c": draws.args(base, std) if drawn_noise else None,
+                  "noise_f": draws.args(base, std, fine=True) if drawn_noise else None,
+                  "fused": draws.args(base, std if drawn_noise else 0., perturb=drawn_perturb)}
 
         def run(d):
             res = kernels.render_rays_fused(
@@ -470,25 +500,25 @@ class SSRRenderMixin:
                 packing.packed_for_module(self.ssr_net_fine, d, dev) if self.N_importance > 0 else None,
                 ray_batch, self.N_samples, self.N_importance, t_vals, u, t_rand, noise_c, noise_f,
                 white_bkgd=self.white_bkgd, endpoint=ep, want_raw_coarse=self.return_raw, want_raw_fine=self.return_raw,
-                want_sem=bool(self.enable_semantic))
+                want_sem=bool(self.enable_semantic), draw=None if dr is None else dr["fused"])
             kernels.check_f16_range(res.pop("status", None), "volumetric_rendering", deferrable=t_rand is None and noise_c is None)
             return res
 
         if desc is None:
-            o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None)
+            o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
         elif _wants_grad(self.ssr_net_coarse, self.ssr_net_fine):
             _training_path_notice("volumetric_rendering")
             td = _train_desc(desc)
             if td is None:
-                o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None)
+                o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
             else:       # one read of both networks' f16 range words, after the whole forward has been enqueued (object_level.render_rays)
                 try:
                     with kernels.deferred_range_checks("volumetric_rendering (training step)"):
-                        o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, td)
+                        o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, td, dr)
                 except FloatingPointError as e:
                     import warnings
                     warnings.warn(f"{e}  {FP32_LAYERS_NOTE}")
-                    o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None)
+                    o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
         else:
             o = kernels.with_f32_fallback(desc, run)
         ret = {}
@@ -512,14 +542,17 @@ class SSRRenderMixin:
             for k in ret:
                 if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
                     print(f"! [Numerical Error] {k} contains nan or inf.")
+        if dr is not None and ray_base is None:
+            draws.advance()
         return ret
 
-    def _staged(self, ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, train_desc=None):
+    def _staged(self, ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, train_desc=None, dr=None):
         """trainer.py:717-808 stage by stage, for training steps: HIP sampling, HIP compositing with its HIP backward, each
         network one autograd node with HIP forward and backward (kernels.mlp_train; torch ``forward`` when ``train_desc`` is
         None).  Same keys as kernels.render_rays_fused."""
         rays_o, rays_d, viewdirs = ray_batch[:, 0:3], ray_batch[:, 3:6].contiguous(), ray_batch[:, -3:]
         c_sem = self.num_valid_semantic_class if self.enable_semantic else 0
+        dr = dr or {"perturb": None, "noise_c": None, "noise_f": None}      # (drawn in the kernels: volumetric_rendering)
 
         def query(z, fn, endpoint=False):
             raw = _train_query(train_desc, fn, ray_batch, z, endpoint) if train_desc is not None else None
@@ -532,20 +565,21 @@ class SSRRenderMixin:
                     raw = run_network(pts, viewdirs, fn, self.embed_fn, self.embeddirs_fn, self.netchunk, show_endpoint=endpoint)
             return raw
 
-        z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, False)
+        z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, False, draw=dr["perturb"])
         raw = query(z_vals, self.ssr_net_coarse)
-        c = kernels.composite(raw, z_vals, rays_d, noise_c, self.white_bkgd, n_classes=c_sem)
+        c = kernels.composite(raw, z_vals, rays_d, noise_c, self.white_bkgd, n_classes=c_sem, draw=dr["noise_c"])
         o = {k + "_coarse": v for k, v in c.items()}
         o["raw_coarse"] = raw
         if self.N_importance > 0:
             # the resampled depths carry no gradient (z_samples.detach(), trainer.py:762)
-            z_samples, z_fine, z_std = kernels.sample_fine(z_vals, c["weights"].detach(), u, self.N_importance)
+            z_samples, z_fine, z_std = kernels.sample_fine(z_vals, c["weights"].detach(), u, self.N_importance, draw=dr["perturb"])
             raw = query(z_fine, self.ssr_net_fine, ep)
             # the endpoint feature is the LAST 128 channels of raw (model_utils.py:99-103, a literal 128 there).  A foreign netwidth
             # gives raw another width (W // 2 feature channels): the kernel's feature lanes only take the 256-wide network's layout,
             # the reference's literal slice is evaluated as written for any other
             native_feat = ep and raw.shape[-1] == 11 + c_sem + 128
-            f = kernels.composite(raw, z_fine, rays_d, noise_f, self.white_bkgd, n_classes=c_sem, feat_dim=128 if native_feat else 0)
+            f = kernels.composite(raw, z_fine, rays_d, noise_f, self.white_bkgd, n_classes=c_sem, feat_dim=128 if native_feat else 0,
+                                  draw=dr["noise_f"])
             if ep and not native_feat:
                 f["feat"] = torch.sum(f["weights"][..., None] * raw[..., -128:], -2)
             o.update({k + "_fine": v for k, v in f.items()})

@@ -8,6 +8,10 @@ cluster MSE, the SSR cross-entropy) instead of the default stand-in loss - once 
 and once on the two launches of csrc/losses.hip, alternating in the same process.
 ``--optimizer inerf`` (with ``--loss intrinsic``) adds a third step to that alternation: the HIP loss with ``optim.Adam``
 (csrc/adam.hip) in place of torch.optim.Adam over the same parameters - the step next to it is its parent figure on the same box.
+``--draws kernel`` (with ``--loss intrinsic``) adds the last step of that alternation once more with the random tensors of the render
+(jitter, inverse-CDF variates, density noise) drawn inside the kernels (``draws.DrawState``, csrc/draws.h) instead of by torch's
+generator - the step next to it is its parent figure - and, with ``--graph``, both of them as HIP graphs (graphs.GraphedTrainStep).
+``--count-launches`` prints the number of device kernels one step of each kind launches (torch.profiler).
 ``--batch inerf`` times the whole object-level step with its batch assembled per iteration - once by the trainer's host + torch
 expressions (scripts/torch_batches.py: image upload, whole-frame rays, host permutation, gathers) and once by
 ``batches.ObjectBatcher.next()`` (csrc/batch.hip) - alternating in the same process; 100 images of 400 x 400 (``--frame``).
@@ -35,7 +39,14 @@ ap.add_argument("--loss", choices=("mse", "intrinsic"), default="mse", help="int
 ap.add_argument("--optimizer", choices=("torch", "inerf"), default="torch", help="inerf: also time the step with optim.Adam (needs --loss intrinsic)")
 ap.add_argument("--batch", choices=("fixed", "inerf"), default="fixed", help="inerf: assemble the batch every step, reference expressions against batches.ObjectBatcher")
 ap.add_argument("--frame", type=int, default=400, help="frame size of --batch inerf")
+ap.add_argument("--draws", choices=("torch", "kernel"), default="torch", help="kernel: also time the step with the render's random tensors drawn in the kernels (needs --loss intrinsic)")
+ap.add_argument("--graph", action="store_true", help="with --draws kernel: also time both steps as HIP graphs")
+ap.add_argument("--count-launches", action="store_true", help="print the device kernels per step of every timed kind")
 a = ap.parse_args()
+if a.draws == "kernel" and a.loss != "intrinsic":
+    raise SystemExit("--draws kernel is timed next to torch's generator inside the --loss intrinsic alternation")
+if a.graph and a.draws != "kernel":
+    raise SystemExit("--graph times the graphed steps of --draws kernel")
 if a.optimizer == "inerf" and a.loss != "intrinsic":
     raise SystemExit("--optimizer inerf is timed next to torch.optim.Adam inside the --loss intrinsic alternation")
 if a.batch == "inerf" and (a.ssr >= 0 or a.loss != "mse" or a.optimizer != "torch"):
@@ -59,6 +70,30 @@ def time_both(steps, iters, what, label="intrinsic loss as"):
             torch.cuda.synchronize(); times[k].append((time.perf_counter() - t0) / iters * 1e3)
     for k, v in times.items():
         print(f"{what}, {label} {k}: {statistics.median(v):.2f} ms per step (rounds: {', '.join(f'{x:.2f}' for x in v)})")
+    if a.count_launches:
+        from torch.profiler import ProfilerActivity, profile
+        for k, fn in steps.items():
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                fn()
+                torch.cuda.synchronize()
+            kernels_seen = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()
+                            and "memset" not in e.name.lower()]
+            print(f"{what}, {label} {k}: {len(kernels_seen)} device kernels per step")
+
+
+def add_draws_steps(steps, make_step, make_opt, example_inputs, dev):
+    """--draws kernel: the last step of ``steps`` again with a DrawState; --graph: that step and its parent as HIP graphs.
+    ``make_step(draws)`` -> (loss_fn(*inputs) that renders with ``draws`` and returns the loss, eager step function using ``opt``)."""
+    from intrinsicnerf_amd import draws, graphs
+    base = list(steps)[-1]
+    state = draws.DrawState(torch.initial_seed(), dev)
+    steps[base + " + kernel draws"] = make_step(state, make_opt())[1]
+    if a.graph:
+        for name, st in ((base + ", graphed", None), (base + " + kernel draws, graphed", draws.DrawState(torch.initial_seed(), dev))):
+            opt_g = make_opt()
+            g = graphs.GraphedTrainStep(make_step(st, opt_g)[0], example_inputs, opt_g, draws=st)
+            steps[name] = (lambda g=g: g(*example_inputs))
 
 
 dev = torch.device("cuda:0")
@@ -108,6 +143,28 @@ if a.ssr >= 0:          # trainer.py:876-991: 1024 rays (512 + neighbours), dept
                 from intrinsicnerf_amd import optim
                 opt_inerf = optim.Adam(list(r.ssr_net_coarse.parameters()) + list(r.ssr_net_fine.parameters()), lr=5e-4)
                 steps["HIP launches + optim.Adam"] = lambda: istep(True, opt_inerf)
+            if a.draws == "kernel":
+                def make_opt():
+                    params = list(r.ssr_net_coarse.parameters()) + list(r.ssr_net_fine.parameters())
+                    if a.optimizer == "inerf":
+                        from intrinsicnerf_amd import optim
+                        return optim.Adam(params, lr=5e-4)
+                    return torch.optim.Adam(params, lr=5e-4, capturable=a.graph)
+
+                def make_step(state, opt_d):
+                    def loss_fn(rb, tg):
+                        r.draws = state
+                        try:
+                            ret = r.render_rays(rb)
+                        finally:
+                            r.draws = None
+                        return ssr.ssr_step_loss(ret, tg, labels, LOSS_WEIGHTS, cluster_target, semantic=a.ssr > 0)[0]
+
+                    def eager():
+                        loss = loss_fn(rays, target)
+                        opt_d.zero_grad(); loss.backward(); opt_d.step()
+                    return loss_fn, eager
+                add_draws_steps(steps, make_step, make_opt, (rays, target), dev)
             time_both(steps, a.iters,
                       f"SSR training step (C = {a.ssr}), {n} rays x (64+128) samples")
         sys.exit(0)
@@ -204,6 +261,25 @@ if a.loss == "intrinsic":
             from intrinsicnerf_amd import optim
             opt_inerf = optim.Adam(list(net_c.parameters()) + list(net_f.parameters()), lr=5e-4)
             steps["HIP launches + optim.Adam"] = lambda: istep(True, opt_inerf)
+        if a.draws == "kernel":
+            def make_opt():
+                params = list(net_c.parameters()) + list(net_f.parameters())
+                if a.optimizer == "inerf":
+                    from intrinsicnerf_amd import optim
+                    return optim.Adam(params, lr=5e-4)
+                return torch.optim.Adam(params, lr=5e-4, capturable=a.graph)
+
+            def make_step(state, opt_d):
+                def loss_fn(rb, tg):
+                    ret = ol.render_rays(rb, net_c, q, 64, retraw=True, perturb=1.0, N_importance=128, network_fine=net_f, white_bkgd=True,
+                                         raw_noise_std=0.0, draws=state)
+                    return ol.object_step_loss(ret, tg, mask, LOSS_WEIGHTS, cluster_target)[0]
+
+                def eager():
+                    loss = loss_fn(rays, target)
+                    opt_d.zero_grad(); loss.backward(); opt_d.step()
+                return loss_fn, eager
+            add_draws_steps(steps, make_step, make_opt, (rays, target), dev)
         time_both(steps, a.iters,
                   f"training step (staged path), {n} rays x (64+128) samples")
     sys.exit(0)
@@ -226,13 +302,22 @@ z = torch.sort(torch.rand(n * 16, s, device=dev) * 4 + 2, -1)[0]
 dd = torch.randn(n * 16, 3, device=dev)
 grads = {k: torch.randn(n * 16, 3, device=dev) for k in ("rgb", "albedo", "residual")}
 grads.update({k: torch.randn(n * 16, device=dev) for k in ("acc", "depth", "shading")})
+# ... and with density noise: read from a tensor (the classic form) against regenerated in the kernel (draws.h: a Philox block per lane)
+from intrinsicnerf_amd import draws as inerf_draws  # noqa: E402
+state = inerf_draws.DrawState(1, dev)
+noise = state.fill(inerf_draws.NOISE_FINE, n * 16, s)
+drawn = state.args(0, 1.0, fine=True)
 for name, fn, nbytes in (("k_composite", lambda: kernels.composite(raw, z, dd, None, True), raw.numel() * 4 + 2 * z.numel() * 4),
-                         ("k_composite_bwd", lambda: kernels.composite_backward(raw, z, dd, grads, None, True), 2 * raw.numel() * 4 + z.numel() * 4)):
+                         ("k_composite, noise tensor", lambda: kernels.composite(raw, z, dd, noise, True), raw.numel() * 4 + 3 * z.numel() * 4),
+                         ("k_composite, drawn noise", lambda: kernels.composite(raw, z, dd, None, True, draw=drawn), raw.numel() * 4 + 2 * z.numel() * 4),
+                         ("k_composite_bwd", lambda: kernels.composite_backward(raw, z, dd, grads, None, True), 2 * raw.numel() * 4 + z.numel() * 4),
+                         ("k_composite_bwd, noise tensor", lambda: kernels.composite_backward(raw, z, dd, grads, noise, True), 2 * raw.numel() * 4 + 2 * z.numel() * 4),
+                         ("k_composite_bwd, drawn noise", lambda: kernels.composite_backward(raw, z, dd, grads, None, True, draw=drawn), 2 * raw.numel() * 4 + z.numel() * 4)):
     fn(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(5):
+    for _ in range(20):
         fn()
     e1.record(); e1.synchronize()
-    ms = e0.elapsed_time(e1) / 5
+    ms = e0.elapsed_time(e1) / 20
     print(f"{name}: {n * 16} rays x {s} samples x {chn} ch: {ms:.3f} ms -> {nbytes / ms / 1e6:.0f} GB/s algorithmic")
