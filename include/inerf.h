@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40014
+#define INERF_ABI_VERSION 40015
 
 /* error codes */
 #define INERF_OK              0
@@ -576,6 +576,43 @@ typedef struct inerf_cluster_fit_args {
 /* workspace of inerf_cluster_fit in bytes (negative INERF_E_* for bad sizes); n_sample_idx = total subsample indices */
 int64_t inerf_cluster_fit_workspace_bytes(int64_t n_pixels, int n_classes, int64_t n_sample_idx);
 int inerf_cluster_fit(const inerf_cluster_fit_args* args, void* stream);
+
+/* Cluster refresh on the device: the pass of render_path(update_cluster=True) (run_nerf.py:142-272, trainer.py:1221-1443)
+ * either side of inerf_cluster_fit.
+ *
+ * inerf_frame_subsample: the fit's sample set of one rendered frame.  frame = the frame's maps side by side, one row of
+ *   `row_stride` floats per pixel (frames.pack_maps), height * width rows.  Every pixel (r, c) with r % step == 0 and
+ *   c % step == 0, in row-major order - albedos[-1][::step, ::step, :].reshape(-1, 3) (run_nerf.py:176, trainer.py:1287) -
+ *   writes its columns albedo_col .. albedo_col + 2 to out_pixels[row, 3] and, with label_col >= 0, its label column
+ *   (a float holding an exact small integer, truncated to int64) to out_labels[row]; the caller passes both pointers
+ *   already advanced to the frame's place in the table.  ceil(height / step) * ceil(width / step) rows are written.
+ *   With label_col >= 0 and class_counts != NULL every label in [0, n_classes) also adds one to class_counts[label]
+ *   (int32, zeroed by the caller once per pass): np.bincount(lab[(lab >= 0) & (lab < K)], minlength=K), integer atomics.
+ *   label_col = -1: out_labels and class_counts are not touched (may be NULL).
+ *   INERF_E_INVALID: a negative height or width, step < 1, a null frame / out_pixels (/ out_labels with a label column),
+ *   a column outside the row, n_classes < 1 with counts, pointers not aligned to their element; a zero-sized frame is
+ *   INERF_OK whatever the pointers; INERF_E_UNSUPPORTED: more than 2^31 - 1 blocks of 256 rows. */
+int inerf_frame_subsample(const float* frame, int64_t row_stride, int albedo_col, int label_col, int height, int width, int step,
+                          float* out_pixels, int64_t* out_labels, int32_t* class_counts, int n_classes, void* stream);
+
+/* inerf_cluster_snap_compose: dest_color of every pixel of a frame and the two 8-bit images the pass writes from it
+ *   (run_nerf.py:226-241, trainer.py:1425-1440).  albedo (3 floats), label (1 float, an exact small integer truncated to
+ *   int64; ignored - may be NULL - with INERF_CLUSTER_IGNORE_LABEL), shading (1 float) and residual (3 floats) point at
+ *   the first pixel's values; consecutive pixels are `row_stride` floats apart for all four (columns of one packed frame).
+ *   The cluster tables are inerf_cluster_lookup's, and so are the search, its argmin and its NaN rule:
+ *     snapped = rgb_centers[links[argmin]] of the pixel's class - the albedo itself where its label has no cluster
+ *     out_c[n,3]    = to8b(snapped)
+ *     out_edit[n,3] = to8b(snapped * shading + residual)   one fp32 product, one fp32 sum, as numpy rounds them
+ *   to8b as inerf_frame_to_u8: (uint8)(255 * clip(x, 0, 1)), NaN -> 0.  out_color[n,3] (fp32, optional, may be NULL)
+ *   receives `snapped`; without it neither the float colour nor the float edit image is written anywhere.
+ *   INERF_E_INVALID: a null pointer (out_color excepted), n_pixels < 0, row_stride < 3, n_classes < 1, anchors not
+ *   16-byte aligned, any other pointer - out_c and out_edit included - not 4-byte aligned; n_pixels == 0 is INERF_OK
+ *   whatever the pointers; INERF_E_UNSUPPORTED: more than 2^31 - 1 blocks. */
+int inerf_cluster_snap_compose(const float* albedo, const float* label, const float* shading, const float* residual,
+                               int64_t row_stride, int64_t n_pixels, const float* anchors, const int32_t* links,
+                               const int32_t* anchor_begin, const float* factor, const float* centers,
+                               const int32_t* center_begin, int n_classes, uint32_t flags, unsigned char* out_c,
+                               unsigned char* out_edit, float* out_color, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Networks outside the fused architecture, and fp32 training batches: one launch per nn.Linear on the fp32 matrix core.

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40014          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40015          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -175,6 +175,8 @@ SYMBOLS = {
     "inerf_cluster_lookup": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _P]),
     "inerf_cluster_fit_workspace_bytes": (_L, [_L, _I, _L]),
     "inerf_cluster_fit": (_I, [C.POINTER(ClusterFitArgs), _P]),
+    "inerf_frame_subsample": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "inerf_cluster_snap_compose": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _P, _P]),
     "inerf_linear": (_I, [C.POINTER(LinearArgs), _P]),
     "inerf_linear_wgrad_workspace_bytes": (_L, [_L, _I, _I]),
     "inerf_linear_wgrad": (_I, [_P, _L, _I, _P, _L, _I, _L, _P, _P, _I, _P, _L, _P]),

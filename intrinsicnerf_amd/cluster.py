@@ -190,9 +190,12 @@ def _device_of(device):
     return device
 
 
-def fit(pixels, labels, class_num, factors, device=None, quantile=0.3, n_samples=5000, band_factor=0.5, sample=None):
+def fit(pixels, labels, class_num, factors, device=None, quantile=0.3, n_samples=5000, band_factor=0.5, sample=None, counts=None):
     """Mean-shift clusters of every class: ``labels`` None = every pixel in class 0 (the SSR ``class_num == 1`` path);
-    ``factors`` = intensity_factor per class; ``sample`` = (indices, begin) to override ``sample_indices``."""
+    ``factors`` = intensity_factor per class; ``sample`` = (indices, begin) to override ``sample_indices``.  ``counts`` = the
+    pixels of each class, ``np.bincount(labels[(labels >= 0) & (labels < K)], minlength=K)``, for ``labels`` that are an integer
+    tensor on the device (``kernels.frame_subsample`` counts while it writes them): the labels then stay where they are - only
+    those K numbers are read on the host."""
     device = _device_of(device)
     K = int(class_num)
     if isinstance(pixels, torch.Tensor):
@@ -203,6 +206,15 @@ def fit(pixels, labels, class_num, factors, device=None, quantile=0.3, n_samples
     if labels is None:
         lab_host, lab_dev = None, None
         counts = np.array([n] + [0] * (K - 1), np.int64)
+    elif counts is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and not labels.is_floating_point()):
+            raise ValueError("counts goes with labels that are an integer tensor on the device")
+        lab_dev = labels.detach().reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+        if lab_dev.shape[0] != n:
+            raise ValueError(f"{lab_dev.shape[0]} labels for {n} pixels")
+        counts = (counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)).reshape(-1).astype(np.int64)
+        if counts.shape[0] != K or (counts < 0).any() or int(counts.sum()) > n:
+            raise ValueError(f"counts must hold the pixels of each of the {K} classes ({n} pixels in all)")
     else:
         lab_host = (labels.detach().reshape(-1).cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels).reshape(-1))
         lab_host = lab_host.astype(np.int64)
@@ -294,17 +306,17 @@ def _cluster_factory(manager, device):
     return cls
 
 
-def update_center(manager, labels, pixels, quantile=0.3, n_samples=5000, band_factor=0.5, cluster_factory=None):
+def update_center(manager, labels, pixels, quantile=0.3, n_samples=5000, band_factor=0.5, cluster_factory=None, counts=None):
     """``Cluster_Manager.update_center`` (SSR/training/cluster.py:52-70) on the GPU for any object with the reference's
     attributes: ``manager.clusters`` becomes one fitted cluster per class (``None`` for a class without pixels).  With
-    ``class_num == 1`` every pixel is fitted and the labels are ignored (:55-59)."""
+    ``class_num == 1`` every pixel is fitted and the labels are ignored (:55-59).  ``counts``: see ``fit``."""
     K = int(manager.class_num)
     device = _device_of(getattr(manager, "device", None))
     make = cluster_factory or _cluster_factory(manager, device)
     first = make()
     factor = float(getattr(first, "intensity_factor", 0.5))          # Cluster() defaults: the reference fits with 0.5
     res = fit(pixels, None if K == 1 else labels, K, [factor] * K, device=getattr(first, "device", device), quantile=quantile,
-              n_samples=n_samples, band_factor=band_factor)
+              n_samples=n_samples, band_factor=band_factor, counts=None if K == 1 else counts)
     clusters = []
     for c in range(K):
         if res.centers[c] is None:

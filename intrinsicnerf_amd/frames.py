@@ -40,7 +40,10 @@ class FrameStreamer:
 
     def push(self, pack):
         out = None
-        if len(self.slots) < self.depth:
+        free = [s for s in range(len(self.slots)) if s not in self.pending]      # slots emptied by pop()
+        if free:
+            slot = free[0]
+        elif len(self.slots) < self.depth:
             self.slots.append([torch.empty(pack.shape, dtype=pack.dtype, pin_memory=True), torch.cuda.Event(), None])
             slot = len(self.slots) - 1
         else:
@@ -58,6 +61,11 @@ class FrameStreamer:
         self.slots[slot][2] = pack                                  # keep the device tensor alive until then
         self.pending.append(slot)
         return out
+
+    def pop(self):
+        """The oldest frame in flight (waits for its copy alone); None when nothing is in flight.  With ``depth`` >= 2 a caller
+        that pushes frame i + 1 before it pops frame i works on a frame while the next one is computed and copied."""
+        return self._collect(self.pending.pop(0)) if self.pending else None
 
     def drain(self):
         out = [self._collect(s) for s in self.pending]

@@ -162,6 +162,81 @@ def frame_to_u8(values):
     return out
 
 
+def frame_subsample(frame, height, width, albedo_col, out_pixels, offset=0, label_col=-1, out_labels=None, class_counts=None, step=2):
+    """Every ``step``-th pixel of a packed frame (``frames.pack_maps``: [height * width, row_stride] fp32) into the cluster fit's
+    sample table (``inerf_frame_subsample``): rows ``offset ..`` of ``out_pixels`` [N, 3] receive
+    ``albedo[::step, ::step].reshape(-1, 3)`` and, with a label column, the same rows of ``out_labels`` [N] (int64) the
+    truncated labels, while ``class_counts`` [K] (int32) gains the bincount of those inside [0, K).  Returns the rows written."""
+    frame = _dev(frame, "frame", (int(height) * int(width), None))
+    out_pixels = _dev(out_pixels, "out_pixels", (None, 3))
+    rows = -(-int(height) // int(step)) * -(-int(width) // int(step)) if step >= 1 else 0
+    offset = int(offset)
+    if offset < 0 or offset + rows > out_pixels.shape[0] or out_pixels.device != frame.device:
+        raise ValueError(f"out_pixels holds {out_pixels.shape[0]} rows on {out_pixels.device}: rows {offset} .. {offset + rows} of a frame on {frame.device}")
+    labelled = label_col is not None and int(label_col) >= 0
+    lab_ptr = cnt_ptr = None
+    k = 0
+    if labelled:
+        if not (isinstance(out_labels, torch.Tensor) and out_labels.dtype == torch.int64 and out_labels.dim() == 1 and out_labels.is_contiguous()
+                and out_labels.device == frame.device and out_labels.shape[0] >= offset + rows):
+            raise ValueError("out_labels must be a contiguous int64 vector on the frame's device, as long as out_pixels")
+        lab_ptr = C.c_void_p(out_labels.data_ptr() + 8 * offset)
+        if class_counts is not None:
+            if not (isinstance(class_counts, torch.Tensor) and class_counts.dtype == torch.int32 and class_counts.dim() == 1
+                    and class_counts.is_contiguous() and class_counts.device == frame.device):
+                raise ValueError("class_counts must be a contiguous int32 vector on the frame's device")
+            cnt_ptr, k = _ptr(class_counts), class_counts.shape[0]
+    with torch.cuda.device(frame.device):
+        rc = _capi.lib().inerf_frame_subsample(_ptr(frame), frame.shape[1], int(albedo_col), int(label_col) if labelled else -1, int(height),
+                                               int(width), int(step), C.c_void_p(out_pixels.data_ptr() + 12 * offset), lab_ptr, cnt_ptr, k,
+                                               _stream(frame))
+    _capi.check(rc, "inerf_frame_subsample")
+    return rows
+
+
+def snap_row_bytes(n):
+    """Bytes per image of ``cluster_snap_compose``'s output buffer: 3 * n rounded up to the kernel's dword stores."""
+    return (3 * int(n) + 3) & ~3
+
+
+def snap_images(out, n):
+    """The two [n, 3] uint8 images inside ``cluster_snap_compose``'s buffer (a tensor, or its host copy as a numpy array)."""
+    return out[0, :3 * n].reshape(n, 3), out[1, :3 * n].reshape(n, 3)
+
+
+def cluster_snap_compose(tables, pack, albedo_col, shading_col, residual_col, label_col=-1, out=None, want_color=False):
+    """A frame's albedo snapped to its cluster centres and the image re-composed from it, as 8-bit images, in one launch of
+    ``inerf_cluster_snap_compose``: ``pack`` is [n, row_stride] fp32 holding the albedo (3), shading (1) and residual (3) columns
+    and - ``label_col >= 0`` - a float label column; without one every pixel belongs to class 0 (``dest_color``'s ``class_num == 1``
+    shortcut).  ``tables``: ``cluster.ClusterTables``.  Returns ``(out, colour)``: ``out`` [2, snap_row_bytes(n)] uint8, one buffer for
+    one device->host copy - ``out[0, :3 * n]`` = to8b(clustered) and ``out[1, :3 * n]`` = to8b(clustered * shading + residual) as
+    [n, 3] images (``snap_images``); ``colour`` [n, 3] fp32 = ``cluster.lookup``'s, only with ``want_color``."""
+    pack = _dev(pack, "pack", (None, None))
+    n, stride = pack.shape
+    if pack.device != tables.device:
+        raise ValueError(f"pack is on {pack.device}, the cluster tables on {tables.device}")
+    labelled = label_col is not None and int(label_col) >= 0
+    for name, col, w in (("albedo", albedo_col, 3), ("shading", shading_col, 1), ("residual", residual_col, 3)) + ((("label", label_col, 1),) if labelled else ()):
+        if not 0 <= int(col) <= stride - w:
+            raise ValueError(f"{name}_col={col} lies outside a row of {stride} floats")
+    row = snap_row_bytes(n)
+    if out is None:
+        out = torch.empty(2, row, dtype=torch.uint8, device=pack.device)
+    elif not (out.dtype == torch.uint8 and tuple(out.shape) == (2, row) and out.is_contiguous() and out.device == pack.device):
+        raise ValueError(f"out must be a contiguous [2, {row}] uint8 tensor on {pack.device}")
+    color = torch.empty(n, 3, dtype=torch.float32, device=pack.device) if want_color else None
+    base = pack.data_ptr()
+    at = lambda col: C.c_void_p(base + 4 * int(col))
+    with torch.cuda.device(pack.device):
+        rc = _capi.lib().inerf_cluster_snap_compose(
+            at(albedo_col), at(label_col) if labelled else None, at(shading_col), at(residual_col), stride, n, _ptr(tables.anchors),
+            _ptr(tables.links), _ptr(tables.anchor_begin), _ptr(tables.factor), _ptr(tables.centers), _ptr(tables.center_begin),
+            tables.n_classes, 0 if labelled else _capi.CLUSTER_IGNORE_LABEL, C.c_void_p(out.data_ptr()),
+            C.c_void_p(out.data_ptr() + row), _ptr(color), _stream(pack))
+    _capi.check(rc, "inerf_cluster_snap_compose")
+    return out, color
+
+
 def _new_status(like):
     return torch.zeros(1, dtype=torch.int32, device=like.device)
 

@@ -23,6 +23,12 @@ reference's own code looks them up in - and then executes the script's own main 
 (csrc/cluster_fit.hip), and with ``--inerf-render-path`` the mirrors' ``render_path`` builds the package's
 ``Cluster_Manager``.
 
+``--inerf-cluster-refresh`` (opt-in; takes effect only together with ``--inerf-render-path``, and implies ``--inerf-cluster-fit``)
+keeps the whole cluster-refresh pass of ``render_path(update_cluster=True)`` on the device (``refresh.ClusterRefresh``,
+csrc/refresh.hip): the mirrors' ``render_path`` gets ``refresh=`` (object level) and ``SSRTrainer.cluster_refresh`` (SSR), each
+a ``ClusterRefresh`` - every second albedo pixel goes into the fit's sample table as its frame is rendered, the fit reads the table
+where it is, and ``c###.png`` / ``edit###.png`` come back as 8-bit images.  Same files, same returned manager.
+
 ``--inerf-losses`` (opt-in) moves the intrinsic loss terms onto the GPU kernels of csrc/losses.hip: ``compute_intrinsic_loss``
 becomes ``losses.compute_intrinsic_loss`` where the trainers look it up - ``run_nerf.py``'s own namespace
 (``from run_nerf_helpers import *``, called at run_nerf.py:977,1007) and ``SSR.training.trainer`` (imported by name at
@@ -164,9 +170,10 @@ class _TrainerDraws:
         return state
 
 
-def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False):
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False, cluster_refresh=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
+    cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
     names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ()) + ((LOSS_SYMBOL,) if losses else ())
     for name in names:
         namespace[name] = getattr(object_level, name)
@@ -185,13 +192,18 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
         import functools
         from . import cluster as inerf_cluster
         factory = inerf_cluster.Cluster_Manager if cluster_fit else namespace["Cluster_Manager"]
-        namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=factory)
+        extra = {}
+        if cluster_refresh:
+            from . import refresh
+            extra["refresh"] = refresh.ClusterRefresh(manager_factory=factory)
+        namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=factory, **extra)
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
+    cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
     bound = {}
     trainer = sys.modules["SSR.training.trainer"]
     methods = SSR_METHODS + (("render_path",) if with_render_path else ())
@@ -203,6 +215,9 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
         # trainer.py:1065 renders with update_cluster = not self.no_cluster: the fitting is the reference's class (trainer.py:16, :1416-1418)
         factory = inerf_cluster.Cluster_Manager if cluster_fit else trainer.Cluster_Manager
         trainer.SSRTrainer.cluster_manager_factory = staticmethod(factory)
+        if cluster_refresh:                            # read by the mirror's render_path (ssr.SSRRenderMixin.cluster_refresh is None)
+            from . import refresh
+            trainer.SSRTrainer.cluster_refresh = refresh.ClusterRefresh(manager_factory=factory)
     bound["SSR.training.trainer.SSRTrainer"] = list(methods)
     for mod_name in SSR_MODULES:
         mod = sys.modules.get(mod_name)
@@ -246,7 +261,7 @@ def _object_batches_notice():
         _told_object_batches = True
 
 
-def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False):
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -260,12 +275,12 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws, cluster_refresh)
         if batches:
             _object_batches_notice()
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws, cluster_refresh)
     return mod, main
 
 
@@ -277,6 +292,9 @@ def main(argv=None):
     cluster_fit = "--inerf-cluster-fit" in argv
     if cluster_fit:
         argv.remove("--inerf-cluster-fit")
+    cluster_refresh = "--inerf-cluster-refresh" in argv
+    if cluster_refresh:
+        argv.remove("--inerf-cluster-refresh")
     losses = "--inerf-losses" in argv
     if losses:
         argv.remove("--inerf-losses")
@@ -301,6 +319,8 @@ def main(argv=None):
         extra["batches"] = True
     if draws:
         extra["draws"] = True
+    if cluster_refresh:
+        extra["cluster_refresh"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

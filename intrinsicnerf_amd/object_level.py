@@ -602,7 +602,7 @@ def to8b(x):
 
 
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0, update_cluster=False,
-                b_f=0.5, cluster_manager_factory=None):
+                b_f=0.5, cluster_manager_factory=None, refresh=None):
     """Render every pose of ``render_poses`` - run_nerf.py:142-272; returns ``(rgbs, disps, cluster_manager)``.
 
     Same arguments, same returned stacks (``[N, H, W, 3]`` / ``[N, H, W]`` float32 numpy), same files in ``savedir``
@@ -611,7 +611,9 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     overlaps the next frame's kernels (frames.FrameStreamer) instead of six blocking ``.cpu()`` calls, and the host
     looks at a frame only after the next one is enqueued.  ``update_cluster`` needs the mean-shift fitting of the
     reference's ``Cluster_Manager.update_center`` (sklearn; training control plane, not rebuilt here): pass the
-    reference's class as ``cluster_manager_factory``."""
+    reference's class as ``cluster_manager_factory``.  ``refresh`` (a ``refresh.ClusterRefresh``; opt-in): with
+    ``update_cluster`` the sample set, the fit and the ``c*`` / ``edit*`` images stay on the device (csrc/refresh.hip) - same
+    returned values, same files; no ``cluster_manager_factory`` is needed then."""
     import os
     from . import frames
     H, W, focal = hwf
@@ -632,17 +634,25 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         label = (m["acc_map"] > 10).astype(int)              # run_nerf.py:173 as written there
         labels.append(label)
         accs.append(label.astype(np.float32))
-        if update_cluster:
+        if update_cluster and not on_device:
             sample_pixels.append(albedos[-1][::2, ::2, :].reshape(-1, 3))
             sample_labels.append(label[::2, ::2].reshape(-1, 1))
         if savedir is not None:
             for prefix, img in (("", rgbs[-1]), ("a", albedos[-1]), ("s", shadings[-1]), ("res", residuals[-1]), ("acc", accs[-1])):
                 frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), frames.to8b(img))
 
+    on_device = bool(update_cluster) and refresh is not None
     streamer, in_flight = None, []
     for i, c2w in enumerate(render_poses):
         out = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
         pack, widths = frames.pack_maps({k: v.detach().reshape(H * W, -1) for k, v in zip(keys, out[:6])}, keys)
+        if on_device:
+            if not pack.is_cuda:
+                raise RuntimeError(f"render_path(refresh=...): the rendered maps live on {pack.device}; the refresh pass runs only on a "
+                                   "HIP device (no CPU / eager fallback exists)")
+            if i == 0:                                   # class_num == 1 (run_nerf.py:218): the (acc > 10) label is not read
+                refresh.begin(len(render_poses), H, W, 1, pack.device)
+            refresh.add_frame(i, pack, widths, keys)
         if pack.is_cuda:
             if streamer is None:
                 streamer = frames.FrameStreamer(pack.device)
@@ -656,7 +666,15 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         for frame in streamer.drain():
             finish(in_flight.pop(0), frame)
     cluster_manager = None
-    if update_cluster:
+    if on_device:
+        # the sample table was filled frame by frame; the fit reads it where it is, and every kept pack becomes its two 8-bit images
+        cluster_manager = refresh.finish(b_f, host=lambda i: (albedos[i], None, shadings[i], residuals[i]))
+        if savedir is not None:
+            for i in range(len(albedos)):
+                c, edit = refresh.snap(i)
+                frames.write_png(os.path.join(savedir, "c{:03d}.png".format(i)), c)
+                frames.write_png(os.path.join(savedir, "edit{:03d}.png".format(i)), edit)
+    elif update_cluster:
         if cluster_manager_factory is None:
             raise NotImplementedError("render_path(update_cluster=True) fits mean-shift clusters (Cluster_Manager.update_center, "
                                       "object_level cluster code of the reference); pass that class as cluster_manager_factory")

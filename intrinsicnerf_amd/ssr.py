@@ -308,6 +308,7 @@ class SSRRenderMixin:
 
     return_raw = True
     check_numerics = True
+    cluster_refresh = None        # a refresh.ClusterRefresh: render_path(update_cluster=True) keeps its sample set, fit and c / edit images on the device
     # a draws.DrawState: in training mode the jitter, the per-ray u (perturb > 0) and the density noise (raw_noise_std > 0) are drawn inside
     # the kernels as a function of (seed, step, stream, global ray index, sample) - the same bits for any `chunk`; None: torch's generator
     draws = None
@@ -340,7 +341,9 @@ class SSRRenderMixin:
         the trainer's own business: ``vis_deps`` / ``vis_entropys`` need ``imgviz.depth2rgb`` (None when imgviz is not
         importable), ``vis_sems`` reads ``self.valid_colour_map`` (None without it).  Reads ``H_scaled, W_scaled, near,
         far`` like the reference.  ``update_cluster`` needs ``self.cluster_manager_factory`` (the reference's
-        ``Cluster_Manager``: its mean-shift fitting is training control plane, not rebuilt here)."""
+        ``Cluster_Manager``: its mean-shift fitting is training control plane, not rebuilt here) - or ``self.cluster_refresh`` (a
+        ``refresh.ClusterRefresh``; opt-in): the sample set, the fit and the ``c*`` / ``edit*`` images then stay on the device
+        (csrc/refresh.hip), with the same returned values and files."""
         import os
         import numpy as np
         from . import frames
@@ -375,7 +378,7 @@ class SSRRenderMixin:
                     acc["vis_sem"].append(cmap[label.astype(np.int64)].astype(np.uint8))
                 if depth2rgb is not None:
                     acc["vis_ent"].append(depth2rgb(acc["ent"][-1]))
-            if update_cluster:
+            if update_cluster and not on_device:
                 sample_pixels.append(acc["albedo"][-1][::2, ::2, :].reshape(-1, 3))
                 sample_labels.append(acc["sem"][-1][::2, ::2].reshape(-1, 1))
             if save_dir is not None:
@@ -392,6 +395,9 @@ class SSRRenderMixin:
                     if acc["vis_ent"]:
                         w("vis_entropy_{:03d}.png", acc["vis_ent"][-1])
 
+        refresh = getattr(self, "cluster_refresh", None)
+        on_device = bool(update_cluster) and refresh is not None
+        class_num = (1 if getattr(self, "no_semantic_tree", False) else self.num_valid_semantic_class) if on_device else None
         streamer, in_flight = None, []
         for i in range(len(rays)):
             out = self.render_rays(rays[i])
@@ -402,6 +408,13 @@ class SSRRenderMixin:
                 maps["sem_label"] = torch.argmax(F.softmax(logits, dim=-1), dim=-1).float()         # < 2^24: exact in fp32
                 maps["sem_entropy"] = torch.sum(-logp * F.softmax(logits, dim=-1), dim=-1)
             pack, widths = frames.pack_maps(maps, keys)
+            if on_device:
+                if not pack.is_cuda:
+                    raise RuntimeError(f"render_path with cluster_refresh: the rendered maps live on {pack.device}; the refresh pass runs "
+                                       "only on a HIP device (no CPU / eager fallback exists)")
+                if i == 0:
+                    refresh.begin(len(rays), H, W, class_num, pack.device)
+                refresh.add_frame(i, pack, widths, keys)
             if pack.is_cuda:
                 if streamer is None:
                     streamer = frames.FrameStreamer(pack.device)
@@ -416,7 +429,16 @@ class SSRRenderMixin:
                 finish(in_flight.pop(0), frame)
         st = lambda name: np.stack(acc[name], 0) if acc[name] else None
         cluster_manager = None
-        if update_cluster:
+        if on_device:
+            # the sample table was filled frame by frame; the fit reads it where it is, and every kept pack becomes its two 8-bit images
+            cluster_manager = refresh.finish(b_f, host=lambda i: (acc["albedo"][i], acc["sem"][i] if class_num > 1 else None,
+                                                                  acc["shading"][i], acc["residual"][i]))
+            if save_dir is not None:
+                for i in range(len(acc["albedo"])):
+                    c, edit = refresh.snap(i)
+                    frames.write_png(os.path.join(save_dir, "c{:03d}.png".format(i)), c)
+                    frames.write_png(os.path.join(save_dir, "edit{:03d}.png".format(i)), edit)
+        elif update_cluster:
             factory = getattr(self, "cluster_manager_factory", None)
             if factory is None:
                 raise NotImplementedError("render_path(update_cluster=True) fits mean-shift clusters (Cluster_Manager.update_center, "
