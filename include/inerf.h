@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40015
+#define INERF_ABI_VERSION 40016
 
 /* error codes */
 #define INERF_OK              0
@@ -60,6 +60,19 @@ extern "C" {
  * ONE deviation: a gated point's heads are not evaluated, so they can neither raise INERF_STATUS_F16_RANGE nor turn a
  * zero-weight term into NaN - either would take a non-finite head activation on a point whose trunk is finite. */
 #define INERF_FLAG_GATE_COLOUR 32u
+/* With INERF_FLAG_GATE_COLOUR only (alone: INERF_E_INVALID): a one-product PROBE of the trunk in front of it.  The gate needs the
+ * sign of sigma, not its value, of every point it culls: a probe kernel evaluates position encoding, the eight layers and the
+ * density head on the f16 hi operands alone (a third of the matrix work), together with S = sum |w_alpha,k| h7_k + |b_alpha|, and
+ * only its CANDIDATES - points with !(s < -kappa S), kappa = 2^-6, the power of two above eight times the largest |s - sigma| / S measured
+ * (profiles/gate_probe_margin.txt); a NaN or an infinity is one - go through the exact trunk, as a list.  A
+ * candidate's raw row is that of INERF_FLAG_GATE_COLOUR alone, bit for bit; a culled point's row is (0, 0, 0, s, 0, ...) with
+ * the probe's s < 0 in place of the exact sigma <= 0, which reaches no map (raw2outputs applies a ReLU to it).
+ * ONE deviation more: on this path the trunk's share of INERF_STATUS_F16_RANGE is decided on the probe's hi-only activations, for
+ * every point, per tile of the probe (the same threshold, 7.5e3 unscaled, a factor 8.7 below f16's maximum; the probe's
+ * activations are within 1e-3 of the exact ones, so the exact trunk cannot overflow on a point the probe did not flag).  The
+ * exact trunk, whose tiles hold candidates of rays from anywhere in a sub-range, raises no flag of its own; the heads do, per point.
+ * inerf_render_rays sets it wherever it sets the gate; INERF_PROBE=0 in the environment turns that off. */
+#define INERF_FLAG_GATE_PROBE 64u
 
 /* arithmetic of the MLP GEMMs (inerf_net_desc.precision) */
 #define INERF_PREC_F32        0   /* v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation             */
@@ -159,6 +172,11 @@ int inerf_encode_mlp_ws(const inerf_net_desc* net, const float* packed_weights, 
 int inerf_encode_mlp_chunked(const inerf_net_desc* net, const float* packed_weights, const float* rays, const float* z_vals,
                              int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/* For tests of INERF_FLAG_GATE_PROBE: the same, and `probe_out` (device, [n_rays * n_samples, 2], or NULL) receives the probe's
+ * (s, S) per point where the probe runs (it is left untouched where the flags do not select it). */
+int inerf_encode_mlp_probed(const inerf_net_desc* net, const float* packed_weights, const float* rays, const float* z_vals,
+                            int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays,
+                            void* workspace, int64_t workspace_bytes, float* probe_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training: what autograd records for the network when the trainers call loss.backward()

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40015          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40016          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -18,6 +18,7 @@ PREC_F32, PREC_F16X3 = 0, 1
 STATUS_F16_RANGE = 1
 FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_ENDPOINT, FLAG_U_PER_RAY, FLAG_BINS_DIRECT = 1, 2, 4, 8, 16
 FLAG_GATE_COLOUR = 32         # inerf_encode_mlp*: colour heads only on points with positive density (include/inerf.h)
+FLAG_GATE_PROBE = 64          # ... with a one-product probe of the trunk in front: only its candidates take the exact trunk
 CLUSTER_IGNORE_LABEL = 1
 CAM_OPENGL = 1
 BASE_CHANNELS, ENDPOINT_DIM, RAY_FLOATS, MAX_CLASSES = 11, 128, 11, 240
@@ -140,6 +141,7 @@ SYMBOLS = {
     "inerf_encode_mlp_workspace_bytes": (_L, [C.POINTER(NetDesc), _L, _I, _U]),
     "inerf_encode_mlp_ws": (_I, [C.POINTER(NetDesc), _P, _P, _P, _L, _I, _U, _P, _P, _P, _L, _P]),
     "inerf_encode_mlp_chunked": (_I, [C.POINTER(NetDesc), _P, _P, _P, _L, _I, _U, _P, _P, _L, _P, _L, _P]),
+    "inerf_encode_mlp_probed": (_I, [C.POINTER(NetDesc), _P, _P, _P, _L, _I, _U, _P, _P, _L, _P, _L, _P, _P]),
     "inerf_mlp_save_floats": (_L, [C.POINTER(NetDesc), _L]),
     "inerf_mlp_save_slot": (_I, [C.POINTER(NetDesc), _I, _L, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "inerf_encode_mlp_train": (_I, [C.POINTER(NetDesc), _P, _P, _P, _L, _I, _U, _P, _P, _P, _P, _P]),

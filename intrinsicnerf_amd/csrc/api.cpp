@@ -25,9 +25,13 @@ enum : unsigned { kHaveZc = 1, kHaveWc = 2, kHaveRawC = 4, kHaveZs = 8, kHaveZf 
 
 // Colour heads only on points with positive density (INERF_FLAG_GATE_COLOUR): a pass is gated when nobody outside the library sees its raw
 // tensor and no noise is added to its sigma; which networks the flag does anything for is inerf_encode_mlp*'s business.  INERF_GATE=0: never.
+// Wherever the gate is set, so is its one-product probe (INERF_FLAG_GATE_PROBE); INERF_PROBE=0: the gate without it.
+constexpr uint32_t kGateFlags = INERF_FLAG_GATE_COLOUR | INERF_FLAG_GATE_PROBE;
 uint32_t gate_flag(bool raw_provided, bool noise) {
     const char* e = std::getenv("INERF_GATE");
-    return (raw_provided || noise || (e && e[0] == '0')) ? 0u : INERF_FLAG_GATE_COLOUR;
+    if (raw_provided || noise || (e && e[0] == '0')) return 0u;
+    const char* pr = std::getenv("INERF_PROBE");
+    return INERF_FLAG_GATE_COLOUR | ((pr && pr[0] == '0') ? 0u : INERF_FLAG_GATE_PROBE);
 }
 
 unsigned provided(const inerf_render_args& a) {
@@ -57,7 +61,7 @@ Plan plan(const inerf_net_desc& net, int64_t n, int sc, int ni, uint32_t flags, 
     }
     // scratch of the encode+MLP launches (the SSR network's channel-split semantic head; the density gate's records - reserved whenever the
     // caller does not take the pass's raw tensor: whether noise keeps the gate off is only known at the call); one region serves both passes
-    const uint32_t mlp_flags = flags & ~INERF_FLAG_GATE_COLOUR;
+    const uint32_t mlp_flags = flags & ~kGateFlags;
     const int64_t ws_c = inerf_encode_mlp_workspace_bytes(&net, n, sc, (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(have & kHaveRawC, false));
     const int64_t ws_f = ni > 0 ? inerf_encode_mlp_workspace_bytes(&net, n, p.s_f, mlp_flags | gate_flag(have & kHaveRawF, false)) : 0;
     p.mlp_ws_bytes = ws_c > ws_f ? ws_c : ws_f;
@@ -126,7 +130,7 @@ static int render_impl(const inerf_render_args* a, const inerf_draw_args* d, voi
     if (rc) return rc;
     float* raw_c = a->raw_coarse ? a->raw_coarse : f(p.raw_c);
     // the coarse net never emits the endpoint feature (trainer.py:751-755: endpoint_feat=False)
-    const uint32_t mlp_flags = a->flags & ~INERF_FLAG_GATE_COLOUR;
+    const uint32_t mlp_flags = a->flags & ~kGateFlags;
     rc = inerf_encode_mlp_chunked(&a->net, a->packed_coarse, a->rays, z_c, n, sc,
                                   (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr || drawn_noise), raw_c, a->status,
                                   a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);

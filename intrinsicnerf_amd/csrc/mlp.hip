@@ -406,7 +406,7 @@ int launch_mlp_f32(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream)
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch = nullptr, int64_t status_rays = 0, void* gate_ws = nullptr);
+                           float* sem_scratch = nullptr, int64_t status_rays = 0, void* gate_ws = nullptr, float* probe_out = nullptr);
 
 // workspace of a launch: the kernels' scratch (sem_scratch_bytes), then - 256-byte aligned - the density gate's buffers
 static bool gated(const inerf_net_desc& net, uint32_t flags) { return (flags & INERF_FLAG_GATE_COLOUR) && inerf::mlp_gate_applies(net, flags); }
@@ -441,6 +441,17 @@ extern "C" int inerf_encode_mlp_chunked(const inerf_net_desc* net, const float* 
     if (need > 0 && (!workspace || workspace_bytes < need)) return INERF_E_WORKSPACE;
     return encode_mlp_impl(net, packed, rays, z, n_rays, n_samples, flags, raw_out, nullptr, nullptr, status, stream,
                            scratch > 0 ? static_cast<float*>(workspace) : nullptr, status_rays, need > scratch ? static_cast<char*>(workspace) + scratch : nullptr);
+}
+
+extern "C" int inerf_encode_mlp_probed(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
+                                       int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays, void* workspace,
+                                       int64_t workspace_bytes, float* probe_out, void* stream) {
+    if (!net || !inerf::net_supported(*net) || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
+    const int64_t need = workspace_need(*net, n_rays, n_samples, flags), scratch = scratch_bytes(*net, n_rays, n_samples, flags);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return INERF_E_WORKSPACE;
+    return encode_mlp_impl(net, packed, rays, z, n_rays, n_samples, flags, raw_out, nullptr, nullptr, status, stream,
+                           scratch > 0 ? static_cast<float*>(workspace) : nullptr, status_rays, need > scratch ? static_cast<char*>(workspace) + scratch : nullptr,
+                           probe_out);
 }
 
 extern "C" int inerf_encode_mlp(const inerf_net_desc* net, const float* packed, const float* rays, const float* z,
@@ -478,8 +489,9 @@ extern "C" int inerf_encode_mlp_train(const inerf_net_desc* net, const float* pa
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch, int64_t status_rays, void* gate_ws) {
+                           float* sem_scratch, int64_t status_rays, void* gate_ws, float* probe_out) {
     using namespace inerf;
+    if ((flags & INERF_FLAG_GATE_PROBE) && !(flags & INERF_FLAG_GATE_COLOUR)) return INERF_E_INVALID;      // the probe is a form of the gate
     if (net && n_rays == 0) return net_supported(*net) ? INERF_OK : INERF_E_UNSUPPORTED;      // empty batch: pointers may be null
     if (!net || !packed || !rays || !z || !raw_out || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
     if (!net_supported(*net)) return INERF_E_UNSUPPORTED;
@@ -505,7 +517,8 @@ static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const
     p.l_xyz = net->l_xyz; p.l_dir = net->l_dir; p.xyz_div = net->xyz_div;
     if (!save && gated(*net, flags)) {      // colour heads only on points with positive density (include/inerf.h INERF_FLAG_GATE_COLOUR)
         if (!gate_ws) return INERF_E_WORKSPACE;
-        return launch_mlp_f16x3_gated(p, n_rays, gate_ws, (hipStream_t)stream);
+        p.probe_out = probe_out;
+        return launch_mlp_f16x3_gated(p, n_rays, gate_ws, (flags & INERF_FLAG_GATE_PROBE) != 0, (hipStream_t)stream);
     }
     return net->precision == INERF_PREC_F16X3 ? launch_mlp_f16x3(p, n_points, ssr, (hipStream_t)stream)
                                               : launch_mlp_f32(p, n_points, ssr, (hipStream_t)stream);

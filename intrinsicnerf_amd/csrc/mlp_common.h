@@ -33,15 +33,20 @@ struct MlpParams {
     unsigned char* gate_rec;        // one 1 KB record (h7: 256 f16 hi | 256 f16 lo) per surviving point, in reservation order
     int* gate_idx;                  // ... and its point index within the sub-range
     unsigned int* gate_count;       // the sub-range's survivor count (zeroed by the launcher)
+    // ... with INERF_FLAG_GATE_PROBE: the probe kernel's candidates, which the listed trunk walks (appended: the fields above keep their offsets)
+    int* cand_idx;                  // point index within the sub-range per candidate, in reservation order
+    unsigned int* cand_count;       // the sub-range's candidate count (zeroed by the launcher)
+    float* probe_out;               // tests only, optional: [n_points, 2] = (s, S) of the probe per point
 };
 
 struct GatePlan {
     int64_t rays_per_sub, n_sub;        // sub-ranges of whole rays
     int64_t idx_off, count_off, bytes;  // workspace: records at 0, point indices, one counter per sub-range
+    int64_t cand_off, cand_count_off;   // ... the probe's candidate list and its counter per sub-range
 };
 GatePlan mlp_gate_plan(int64_t n_rays, int n_samples);
 bool mlp_gate_applies(const inerf_net_desc& net, uint32_t flags);      // which launches the flag changes anything for
-int launch_mlp_f16x3_gated(const MlpParams& p, int64_t n_rays, void* gate_ws, hipStream_t stream);
+int launch_mlp_f16x3_gated(const MlpParams& p, int64_t n_rays, void* gate_ws, bool probe, hipStream_t stream);
 
 // Staggered start of the input-gradient chain.  Every workgroup walks the same stages at the same pace, so the whole chip asks HBM for the same kind of rows at the same moment - 64 KB per CU x 256 CUs is
 // 6 000 cycles of HBM whatever the kernel does meanwhile.  A start offset of ((b ^ (b >> 3)) & 7) x units x 2 048 cycles spreads

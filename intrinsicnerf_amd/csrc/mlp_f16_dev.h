@@ -68,6 +68,17 @@ __device__ __forceinline__ void split_store(_Float16* hi_ptr, float v, float& am
     amax = fmaxf(amax, fabsf(t));
 }
 
+// The density gate's probe: one f16 to nearest, into the hi plane and - the SAME value - into the lo plane, which the one-product trunk
+// never reads as an operand plane: the copy is the encoding parked for the skip layer.
+template <int PLANE = kPlaneH>
+__device__ __forceinline__ void hi_store_parked(_Float16* hi_ptr, float v, float& amax) {
+    const float t = v * kActScale;
+    const _Float16 h = (_Float16)t;
+    hi_ptr[0] = h;
+    hi_ptr[PLANE] = h;
+    amax = fmaxf(amax, fabsf(t));
+}
+
 // sin and cos of an encoding argument a = x * 2^f (|a| up to 6 * 2^9 on the chair scene, 2^9 on the room's x / 10).
 // ocml's sincosf spends ~100 instructions (and diverges into its large-argument path) per call; the encodings are 24
 // calls per sample point.  This is the classic three-constant Cody-Waite reduction, exact to ~6e-8 in the reduced
@@ -134,14 +145,18 @@ __device__ __forceinline__ void wide_prefetch_h(WidePreH<RB>& pre, const WeightB
 // passes the size of one stream).
 // PEEL: the first four k-blocks stand in front of the loop and, with ZERO, the first product of every accumulator takes a zero C operand (an
 // inline constant) instead of 16 * RB * PB v_mov in front of the GEMM - exposed instructions: the matrix pipe is empty until they are through.
+// NPROD: 3 - the split product hi*hi + hi*lo + lo*hi; 1 - hi*hi alone (the density gate's probe, mlp_f16_t128.hip): neither the lo plane
+// nor the lo weight fragments are read, `xl` may point into either plane.
 template <int RB, int KB0, int KB1, int ROW = kRowH, int PLANE = kPlaneH, bool ZERO = true, int KSTRIDE = RB * 2048, int PB = 2, int RBSTRIDE = 2048,
-          bool PEEL = false>
+          bool PEEL = false, int NPROD = 3>
 __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const WeightBuf& wb, int frag_bytes,
                                             const _Float16* xl,      // plane_hi + (lane&31)*kRowH + 8*(lane>>5)
                                             int col0, int col1, int lane, f32x16 (&am)[RB][PB]) {
     constexpr int KBT = KB0 + KB1;
     static_assert(KBT % 2 == 0 && KBT >= 4, "k-block count");
     static_assert(PB == 2 || (PB == 1 && RB == 2) || (PB == 4 && RB == 1), "point blocks");
+    static_assert(NPROD == 3 || (NPROD == 1 && PB == 4 && RB == 1), "the one-product form is the 128-point tile's");
+    constexpr int NP = NPROD == 1 ? 1 : 2;      // operand planes / weight parts read
     if constexpr (ZERO && !PEEL) {
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
@@ -160,11 +175,11 @@ __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const Weigh
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int part = 0; part < 2; ++part) { w[0][rb][part] = pre.w[0][rb][part]; w[1][rb][part] = pre.w[1][rb][part]; }
+        for (int part = 0; part < NP; ++part) { w[0][rb][part] = pre.w[0][rb][part]; w[1][rb][part] = pre.w[1][rb][part]; }
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb)
 #pragma unroll
-        for (int part = 0; part < 2; ++part)
+        for (int part = 0; part < NP; ++part)
             x[0][pb][part] = *reinterpret_cast<const f16x8*>(xl + part * PLANE + xoff(0) + pb * 32 * ROW);
     // PEEL forms: the lo plane through a base register of its own (laundered: derived from `xl` by a constant the compiler re-adds it per read -
     // PLANE is beyond the 64 KB an LDS instruction's immediate offset reaches - 17 v_add per 48 MFMAs of the 128-point tile's loop, now 2)
@@ -187,26 +202,36 @@ __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const Weigh
            the layer's input (inside the row: unused values) */                                                                            \
         const int xo_ = (KB1 == 0 && PEEL) ? col0 + 16 * ((K) + 1) : xoff(k1_);                                      \
         _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                                            \
-            _Pragma("unroll") for (int part = 0; part < 2; ++part)                                                   \
+            _Pragma("unroll") for (int part = 0; part < NP; ++part)                                                  \
                 w[((I) + 2) & 3][rb][part] = wb.frag(frag_bytes + k2_ * KSTRIDE + rb * RBSTRIDE + part * 1024);      \
         _Pragma("unroll") for (int pb = 0; pb < PB; ++pb)                                                            \
-            _Pragma("unroll") for (int part = 0; part < 2; ++part)                                                   \
+            _Pragma("unroll") for (int part = 0; part < NP; ++part)                                                  \
                 x[((I) + 1) & 1][pb][part] =                                                                         \
                     *reinterpret_cast<const f16x8*>((PEEL && part ? xl_lo : xl + part * PLANE) + xo_ + pb * 32 * ROW); \
         /* hi*hi, hi*lo, lo*hi into the same accumulator; product-major: an accumulator is touched every 4th MFMA */ \
         _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                                            \
             _Pragma("unroll") for (int pb = 0; pb < PB; ++pb)                                                        \
                 am[rb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[(I) & 3][rb][0], x[(I) & 1][pb][0], (FIRST) ? zero_c : am[rb][pb], 0, 0, 0); \
+        if constexpr (NPROD == 3) {                                                                                  \
         _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                                            \
             _Pragma("unroll") for (int pb = 0; pb < PB; ++pb)                                                        \
                 am[rb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[(I) & 3][rb][0], x[(I) & 1][pb][1], am[rb][pb], 0, 0, 0); \
         _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                                            \
             _Pragma("unroll") for (int pb = 0; pb < PB; ++pb)                                                        \
                 am[rb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[(I) & 3][rb][1], x[(I) & 1][pb][0], am[rb][pb], 0, 0, 0); \
+        }                                                                                                            \
         /* issue order (masks: 0x8 MFMA, 0x20 VMEM read, 0x100 DS read).  PB = 2: MFMA, global load, MFMA, LDS read(s), MFMA - 2*RB  \
            times; PB = 1 (RB = 2: 6 MFMAs, 4 global loads, 2 LDS reads): MFMA, global load, MFMA, global load, MFMA, LDS read - twice; \
            PB = 4 (RB = 1, the 128-point tile: 12 MFMAs, 2 global loads, 8 LDS reads): the LDS reads (needed one step ahead) first */ \
-        if constexpr (PB == 4) {                                                                                     \
+        if constexpr (NPROD == 1) {     /* 4 MFMAs, 4 LDS reads, 1 global load */                                    \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                       \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \
+        } else if constexpr (PB == 4) {                                                                              \
             _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                         \
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
                 __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                   \
@@ -522,7 +547,9 @@ struct BitsDst {
     int off;                          // bytes: (((tile * kReluBitLayers + layer) * 4 + wave) * 64 + lane) * 8
 };
 
-template <int RB, int ROW = kRowH, int PLANE = kPlaneH, bool SAVE = false, bool BITS = false, int PB = 2, bool MAX3 = true>
+// HI_ONLY (the density gate's probe): bias, ReLU, ONE conversion to f16 - to nearest: the probe shares bits with nothing, and in an fp64
+// emulation of the default-init trunk its distance from the exact sigma is half the truncating form's - and one store into the hi plane.
+template <int RB, int ROW = kRowH, int PLANE = kPlaneH, bool SAVE = false, bool BITS = false, int PB = 2, bool MAX3 = true, bool HI_ONLY = false>
 __device__ __forceinline__ void wide_store_h(const f32x16 (&am)[RB][PB], float inv, const f32x4 (&bias)[RB][4],
                                              _Float16* dl,   // plane_hi + (lane&31)*kRowH + 4*(lane>>5) + dcol + chan0
                                              bool relu, f16x2& amax2, float* gout /* or nullptr: + chan0 + 4*(lane>>5) */,
@@ -545,6 +572,7 @@ __device__ __forceinline__ void wide_store_h(const f32x16 (&am)[RB][PB], float i
     // 64-point tiles - the same bits at the same addresses.
     static_assert(!BITS || (RB == 2 && PB == 2) || (RB == 1 && PB == 4), "mask words are defined for the 64 x 64 and the 32 x 128 wave tile");
     static_assert(PB == 2 || !SAVE, "fp32 row copies are defined for the 64-point tile");
+    static_assert(!HI_ONLY || (!SAVE && !BITS && MAX3), "the hi-only epilogue is an inference form");
     constexpr int kWords = BITS ? RB * PB / 2 : 1;
     unsigned mask[kWords];
 #pragma unroll
@@ -588,6 +616,17 @@ __device__ __forceinline__ void wide_store_h(const f32x16 (&am)[RB][PB], float i
                                                            sv->voff + (pb * 32 * sv->stride + 32 * rb + 8 * g) * 4, 0, 0);
                 }
 #endif
+                if constexpr (HI_ONLY) {
+                    const f16x2 r01 = {(_Float16)t[0], (_Float16)t[1]}, r23 = {(_Float16)t[2], (_Float16)t[3]};
+                    f16x2 b01 = r01, b23 = r23;
+                    if (!relu) {
+                        b01 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, r01) & 0x7FFF7FFFu);
+                        b23 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, r23) & 0x7FFF7FFFu);
+                    }
+                    pk_max3_into(amax2, b01, b23);
+                    *reinterpret_cast<f16x4*>(dl + pb * 32 * ROW + 32 * rb + 8 * g) = f16x4{r01[0], r01[1], r23[0], r23[1]};
+                    continue;
+                }
                 f16x2 h01, h23, l01, l23;
                 split_pair(t[0], t[1], h01, l01);
                 split_pair(t[2], t[3], h23, l23);
@@ -649,17 +688,38 @@ __device__ __forceinline__ f32x4 skinny_gemm_h(const WeightBuf& wb, int frag_byt
     return r;
 }
 
+// The density gate's probe (mlp_f16_t128.hip): row 0 of the same skinny product on hi operands alone, `s`, and the same product on
+// the weight fragments and the bias with their sign bits cleared, `S` = sum |w_k| x_k + |b| (x = relu(...) >= 0): the scale the
+// probe's distance from the split product is a fraction of.  Lanes 0..15: this wave's points.
+template <int KB32>
+__device__ __forceinline__ void skinny_probe_h(const WeightBuf& wb, int frag_bytes, int bias_bytes, int scale_bytes,
+                                               const _Float16* xs /* as skinny_gemm_h */, int lane, float& s, float& S) {
+    const f32x4 bias = wb.vec4(bias_bytes, 16 * (lane >> 4));
+    const float inv = wb.scalar(scale_bytes);
+    f32x4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int kb = 0; kb < KB32; ++kb) {
+        const f16x8 wh = wb.frag(frag_bytes + (2 * kb) * 1024);
+        const f16x8 wa = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, wh) & 0x7FFF7FFFu);
+        const f16x8 xh = *reinterpret_cast<const f16x8*>(xs + 32 * kb);
+        a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa, xh, a1, 0, 0, 0);
+    }
+    s = __builtin_fmaf(a0[0], inv, bias[0]);
+    S = __builtin_fmaf(a1[0], inv, fabsf(bias[0]));
+}
+
 __device__ __forceinline__ float sigmoid_ref_h(float x) { return __fdiv_rn(1.0f, 1.0f + expf(-x)); }
 
 
-template <int RB, int KSTRIDE = RB * 2048, int RBSTRIDE = 2048>
+template <int RB, int KSTRIDE = RB * 2048, int RBSTRIDE = 2048, int NP = 2>      // NP = 1: the hi fragments alone (wide_gemm_h NPROD = 1)
 __device__ __forceinline__ void prefetch_w(WidePreH<RB>& pre, const WeightBuf& wb, int frag_bytes) {
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-            for (int part = 0; part < 2; ++part) pre.w[kb][rb][part] = wb.frag(frag_bytes + kb * KSTRIDE + rb * RBSTRIDE + part * 1024);
+            for (int part = 0; part < NP; ++part) pre.w[kb][rb][part] = wb.frag(frag_bytes + kb * KSTRIDE + rb * RBSTRIDE + part * 1024);
 }
 
 template <int RB>

@@ -90,14 +90,26 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 //   kGateHeads  walks ceil(*gate_count / 128) tiles of records: rows back into the planes, the direction encoding again from point
 //               index -> ray, then the heads; the ten colour channels go to raw[index].  Rows past the count are computed on the last
 //               record and not stored.  The range guard is per POINT here (a tile holds points of rays from anywhere in the launch).
-enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2 };
+//   kGateProbe  (INERF_FLAG_GATE_PROBE) settles sigma's SIGN for most points at a third of the trunk's matrix work: position encoding and the
+//               eight layers on hi operands alone (ONE product per MAC, activations rounded to nearest into the hi plane; the lo plane
+//               holds nothing but a copy of the encoding, which the skip layer reads there), then s = the alpha product on hi operands
+//               and S = the same product on |weights| and |bias|.  raw[pt] = (0, 0, 0, s, 0 ...); a point is a CANDIDATE when
+//               !(s < -kProbeKappa * S) (a NaN or an infinity is one): its index goes into a list, reserved like the records.  Every
+//               other point's exact sigma is negative (the margin: profiles/gate_probe_margin.txt), which is all the frame needs of it.
+//   kGateTrunk with kListed: persistent over ceil(*cand_count / 128) tiles of the candidate list - a row's point comes from the list, its
+//               exact sigma is scattered into that point's raw row, its record carries the original index (the heads kernel is the same).
+//               A point's column of every GEMM depends on that point alone: the same bits as the unlisted trunk's.
+enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3 };
 constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
+// The probe's margin: the smallest power of two >= 8 x the largest |s - sigma| / S measured on the GPU (profiles/gate_probe_margin.txt).
+constexpr float kProbeKappa = 0x1p-6f;
 
-template <bool kSsr, bool kSave, bool kPipe, int kMode>
+template <bool kSsr, bool kSave, bool kPipe, int kMode, bool kListed = false>
 __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     static_assert(!(kSsr && kSave), "the saving form is the object-level network's");
     static_assert(!kPipe || (!kSsr && !kSave), "the pipelined trunk is the object-level inference form");
     static_assert(kMode == kWhole || (!kSsr && !kSave && !kPipe), "the density gate is the object-level inference form's");
+    static_assert(!kListed || kMode == kGateTrunk, "the candidate list feeds the gated trunk");
     constexpr int kParts = 512 / kPtsT;
     // the wide GEMMs' first products take a zero C operand instead of 64 v_mov in front of every GEMM (wide_gemm_h PEEL): +1.3 % same-box,
     // same bits (profiles/r06_peel_ab.txt); the saving form keeps the explicit zeroing like the two-workgroup one
@@ -123,15 +135,21 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
 
     WidePreH<1> pre1;
     WidePreH<2> pre2;
-    if constexpr (kMode == kGateHeads) prefetch_w<2>(pre2, wb, frag256(L.as1, 16));
-    else                               prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
+    if constexpr (kMode == kGateHeads)      prefetch_w<2>(pre2, wb, frag256(L.as1, 16));
+    else if constexpr (kMode == kGateProbe) prefetch_w<1, 4096, 2048, 1>(pre1, wb, frag32(L.trunk[0], 4));
+    else                                    prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
     // gated heads: the survivor count of this sub-launch (written by the trunk kernel in front of it on the stream; never more than its points)
     int n_rec = 0;
     if constexpr (kMode == kGateHeads) {
         n_rec = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<const volatile unsigned*>(p.gate_count));
         n_rec = n_rec < p.n_points ? n_rec : p.n_points;
     }
-    const int n_tiles = kMode == kGateHeads ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
+    // listed trunk: the candidate count of this sub-launch (written by the probe kernel in front of it on the stream), likewise
+    if constexpr (kListed) {
+        n_rec = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<const volatile unsigned*>(p.cand_count));
+        n_rec = n_rec < p.n_points ? n_rec : p.n_points;
+    }
+    const int n_tiles = kMode == kGateHeads || kListed ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
     // the 16 pad bytes behind a row's direction columns (hi plane; no GEMM uses what it reads there).  Gated trunk: rows 0..7 hold the
     // waves' survivor counts, row 8 the tile's first record.  Gated heads: row r holds four words, non-zero when point r left the f16 range
     auto pad_of = [&](int r) { return reinterpret_cast<int*>(ldst + r * kRowD + kWidth + kDirCols); };
@@ -154,6 +172,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             const int pt = tid_o % kPtsT, part = tid_o / kPtsT;
             int gp = tile * kPtsT + pt;
             if constexpr (kMode == kGateHeads) gp = p.gate_idx[gp < n_rec ? gp : n_rec - 1];      // the record's point
+            if constexpr (kListed) gp = p.cand_idx[gp < n_rec ? gp : n_rec - 1];                  // the candidate (rows past the count: the last one)
             gp = gp < p.n_points ? gp : p.n_points - 1;
             int n_samples = p.n_samples;           // (laundered: the division's reciprocal, as a loop invariant, is one more register held - and
             asm volatile("" : "+s"(n_samples));    // at this kernel's 256 spilled - across the whole tile)
@@ -174,17 +193,25 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                     for (int c = 0; c < 3; ++c) {
                         float sn, cs;
                         fast_sincosf(x[c] * s, &sn, &cs);
-                        split_store<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
-                        split_store<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
+                        if constexpr (kMode == kGateProbe) {
+                            hi_store_parked<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
+                            hi_store_parked<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
+                        } else {
+                            split_store<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
+                            split_store<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
+                        }
                     }
                 }
                 if (part == 2) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) split_store<kPlaneT>(row + c, x[c], amax);
+                    for (int c = 0; c < 3; ++c) {
+                        if constexpr (kMode == kGateProbe) hi_store_parked<kPlaneT>(row + c, x[c], amax);
+                        else                               split_store<kPlaneT>(row + c, x[c], amax);
+                    }
                     for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) { row[c] = (_Float16)0.0f; row[kPlaneT + c] = (_Float16)0.0f; }
                 }
             }
-            if constexpr (kMode != kGateTrunk) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
+            if constexpr (kMode != kGateTrunk && kMode != kGateProbe) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
                 const int fd = kParts - 1 - part;
                 if (fd < p.l_dir) {
                     const float s = (float)(1 << fd);
@@ -224,7 +251,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
 #ifdef INERF_ABL_NO_ENCODE      // (timing ablation of a development build: the first tile's encoding stays in LDS; results are wrong)
         if (tile == (int)blockIdx.x)
 #endif
-        encode(kMode != kGateTrunk);
+        encode(kMode != kGateTrunk && kMode != kGateProbe);
         __syncthreads();
         // park the encoding for the skip layer (piece q = tid + 512 i of the tile's 2 048 sixteen-byte pieces: plane q / 1024, row (q % 1024) / 8)
         const bool enc_cached = !kSsr && !kSave && kMode == kWhole && p.sem_scratch != nullptr;
@@ -409,6 +436,35 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             prefetch_w<2>(pre2, wb, frag256(L.as1, 16));                      // (outside the layer loop: assigned inside it the 32 registers are loop-carried)
             pp_epilogue<kRowD, kPlaneT>(accB, inv, bias[0], xdB, amax2);      // E(7,B): nothing left to run it under
             __syncthreads();
+        } else if constexpr (kMode == kGateProbe) {
+            // one product per MAC: the hi plane in place, the skip layer's encoding from its copy in the lo plane (nothing overwrites it)
+            auto pf1 = [&](const GemmSlot& s, int kbt, int kb_first) { prefetch_w<1, 4096, 2048, 1>(pre1, wb, frag32(s, kbt) + kb_first * 4096); };
+            auto store_hi = [&](const GemmSlot& s, const GemmSlot& next, int kbt, int kb_first) {
+                load_bias<1>(bias1, inv1, wb, (s.b + 32 * wave) * 4, (s.b + kWidth) * 4, lane_t);
+                pf1(next, kbt, kb_first);
+                __syncthreads();                       // every wave has read the layer's input
+                wide_store_h<1, kRowD, kPlaneT, false, false, 4, true, true>(am1, inv1, bias1, xd, true, amax2, nullptr, 0, 0, 0);
+                __syncthreads();
+            };
+            wide_gemm_h<1, 4, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[0], 4), xr, 0, 0, lane_t, am1);
+            store_hi(L.trunk[0], L.trunk[1], 16, 0);
+    #pragma unroll 1
+            for (int layer = 1; layer < kSkipInput; ++layer) {
+                wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[layer], 16), xr, 0, 0, lane_t, am1);
+                if (layer + 1 < kSkipInput) store_hi(L.trunk[layer], L.trunk[layer + 1], 16, 0);
+                else                        store_hi(L.trunk[layer], L.trunk[kSkipInput], 20, 4);
+            }
+            {
+                const GemmSlot& s = L.trunk[kSkipInput];
+                wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(s, 20) + 4 * 4096, xr, 0, 0, lane_t, am1);
+                pf1(s, 20, 0);
+                wide_gemm_h<1, 4, 0, kRowD, kPlaneT, false, 4096, 4, 2048, false, 1>(pre1, wb, frag32(s, 20), xr + kPlaneT, 0, 0, lane_t, am1);
+                store_hi(s, L.trunk[6], 16, 0);
+            }
+            wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[6], 16), xr, 0, 0, lane_t, am1);
+            store_hi(L.trunk[6], L.trunk[7], 16, 0);
+            wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[7], 16), xr, 0, 0, lane_t, am1);
+            store_hi(L.trunk[7], L.trunk[0], 4, 0);
         } else {
             wide_gemm_h<1, 4, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[0], 4), xr, 0, 0, lane_t, am1);
             store256(L.trunk[0], true, SAVE_H0, pf32(L.trunk[1], 16), kWithBits);
@@ -436,7 +492,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         }
 
         // ---------------- density gate: sigma, the raw rows, the survivors' records ----------------
-        if constexpr (kMode == kGateTrunk) {
+        if constexpr (kMode == kGateTrunk && !kListed) {
             const int pt16 = tile * kPtsT + 16 * wave;
             const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
             const float sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];   // lanes 0..15: this wave's points
@@ -479,6 +535,76 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p.gate_rec + (size_t)slot * kGateRecordBytes) + lane_t);
             }
             flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
+            __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
+            continue;
+        }
+
+        // ---------------- the same for the probe (s and S, the raw rows, the candidate list) and the listed trunk (sigma scattered, records) ----------------
+        if constexpr (kListed || kMode == kGateProbe) {
+            const int pt16 = tile * kPtsT + 16 * wave;
+            const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
+            float sigma, scale = 0.0f;                 // lanes 0..15: this wave's points
+            if constexpr (kMode == kGateProbe) skinny_probe_h<8>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t, sigma, scale);
+            else sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];
+            const bool valid = lane_t < 16 && pt16 + lane_t < (kListed ? n_rec : p.n_points);
+            const bool keep = valid && (kMode == kGateProbe ? !(sigma < -kProbeKappa * scale) : !(sigma <= 0.0f));
+            const unsigned kept = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep));
+            if (lane_t == 0) pad_of(wave)[0] = __popc(kept);
+            int my_point = pt16 + lane_t;              // the row's point within the sub-range
+            if constexpr (kListed) {                   // exact sigma into the candidate's raw row, whose other ten channels the probe zeroed
+                my_point = p.cand_idx[valid ? pt16 + lane_t : 0];
+                if (valid) __builtin_nontemporal_store(sigma, p.raw + (size_t)my_point * p.channels + 3);
+            } else {
+                // raw: the wave's 16 points x 11 floats as 44 sixteen-byte pieces (like the whole kernel's), sigma in channel 3 of zeros
+                float piece[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = 4 * (lane_t < 44 ? lane_t : 43) + i, pt = e / INERF_BASE_CHANNELS;
+                    const float s_pt = __shfl(sigma, pt);
+                    piece[i] = e - INERF_BASE_CHANNELS * pt == 3 ? s_pt : 0.0f;
+                }
+                if (p.channels == INERF_BASE_CHANNELS && pt16 + 16 <= p.n_points && (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0) {
+                    if (lane_t < 44)
+                        __builtin_nontemporal_store(f32x4{piece[0], piece[1], piece[2], piece[3]},
+                                                    reinterpret_cast<f32x4*>(p.raw + (size_t)pt16 * INERF_BASE_CHANNELS) + lane_t);
+                } else if (lane_t < 16 && pt16 + lane_t < p.n_points) {
+                    float* const out_row = p.raw + (size_t)(pt16 + lane_t) * p.channels;
+#pragma unroll
+                    for (int c = 0; c < INERF_BASE_CHANNELS; ++c) __builtin_nontemporal_store(c == 3 ? sigma : 0.0f, out_row + c);
+                }
+            }
+            if constexpr (kMode == kGateProbe)
+                if (p.probe_out && valid) {            // tests: (s, S) per point
+                    p.probe_out[2 * (size_t)(pt16 + lane_t)] = sigma;
+                    p.probe_out[2 * (size_t)(pt16 + lane_t) + 1] = scale;
+                }
+            __syncthreads();                       // the eight counts are there
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                const int c = pad_of(w)[0];
+                total += c;
+                before += w < wave ? c : 0;
+            }
+            unsigned int* const counter = kMode == kGateProbe ? p.cand_count : p.gate_count;
+            int* const index_list = kMode == kGateProbe ? p.cand_idx : p.gate_idx;
+            if (tid == 0) pad_of(8)[0] = total > 0 ? (int)atomicAdd(counter, (unsigned)total) : 0;
+            __syncthreads();
+            const int slot0 = __builtin_amdgcn_readfirstlane(pad_of(8)[0] + before);      // (<= the launch's points - this wave's survivors: inside the buffers)
+            if (keep) index_list[slot0 + __popc(kept & ((1u << lane_t) - 1u))] = my_point;
+            if constexpr (kMode == kGateTrunk) {
+                int slot = slot0;
+                for (unsigned m = kept; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
+                    const int j = __builtin_ctz(m);
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(ldst + (lane_t >> 5) * kPlaneT + (16 * wave + j) * kRowD + 8 * (lane_t & 31));
+                    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p.gate_rec + (size_t)slot * kGateRecordBytes) + lane_t);
+                }
+            }
+            // The range guard is the PROBE's: it sees every point of the sub-range, a candidate included, in tiles of consecutive rays, and
+            // its hi-only activations are within 1e-3 of the exact ones - with the threshold a factor 8.7 below f16's maximum the exact
+            // trunk cannot overflow on a point the probe did not flag.  A listed tile holds points of rays from anywhere in the sub-range:
+            // a per-tile flag here would mark the words of rays whose own points are in range (and have their chunks rendered again).
+            if constexpr (!kListed) flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
             __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
             continue;
         }
@@ -731,9 +857,12 @@ __global__ __launch_bounds__(512, 2) void k_encode_mlp_f16x3_t128(const MlpParam
 }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_heads_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateHeads>(p); }
+__global__ __launch_bounds__(512, 2) void k_mlp_gate_probe_f16(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateProbe>(p); }
+__global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_listed_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk, true>(p); }
 
 // ---- the density gate's launcher ----
-// A launch is walked in sub-ranges of whole rays, each as trunk kernel then heads kernel on the same stream.  The record buffer holds one
+// A launch is walked in sub-ranges of whole rays, each as trunk kernel then heads kernel on the same stream (with the probe: probe kernel,
+// listed trunk, heads; the candidate list holds one index per point of a sub-range, so it cannot overflow either).  The record buffer holds one
 // record per POINT of a sub-range - every point surviving is the worst case - so it cannot overflow.  Its size comes from a byte budget:
 // INERF_GATE_BYTES, default 2 GiB = 2 M points = 64 tiles per CU per trunk launch (DESIGN.md 3.1c on the tail that implies).
 static int64_t gate_budget_points() {
@@ -759,20 +888,28 @@ GatePlan mlp_gate_plan(int64_t n_rays, int n_samples) {
     auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
     g.idx_off = up(pts * kGateRecordBytes);
     g.count_off = g.idx_off + up(pts * 4);
-    g.bytes = g.count_off + up(g.n_sub * 4);
+    // (the probe's candidate list and counters come behind the budgeted part: the sub-ranges are the same with and without the probe)
+    g.cand_off = g.count_off + up(g.n_sub * 4);
+    g.cand_count_off = g.cand_off + up(pts * 4);
+    g.bytes = g.cand_count_off + up(g.n_sub * 4);
     return g;
 }
 
-int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, hipStream_t stream) {
+// `probe` (INERF_FLAG_GATE_PROBE): probe kernel -> listed trunk -> heads per sub-range instead of trunk -> heads.
+int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, bool probe, hipStream_t stream) {
     const GatePlan g = mlp_gate_plan(n_rays, p0.n_samples);
     char* const ws = static_cast<char*>(gate_ws);
     unsigned int* const counts = reinterpret_cast<unsigned int*>(ws + g.count_off);
+    unsigned int* const cand_counts = reinterpret_cast<unsigned int*>(ws + g.cand_count_off);
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)g.n_sub * 4, stream);
+    if (e == hipSuccess && probe) e = hipMemsetAsync(cand_counts, 0, (size_t)g.n_sub * 4, stream);
     if (e != hipSuccess) return record(e);
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_heads_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_probe_f16), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_listed_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
         if (e != hipSuccess) return record(e);
         attr_set.mark();
     }
@@ -788,19 +925,32 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, h
         p.gate_rec = reinterpret_cast<unsigned char*>(ws);
         p.gate_idx = reinterpret_cast<int*>(ws + g.idx_off);
         p.gate_count = counts + s;
+        p.cand_idx = reinterpret_cast<int*>(ws + g.cand_off);
+        p.cand_count = cand_counts + s;
+        if (p.probe_out) p.probe_out = p0.probe_out + 2 * r0 * p0.n_samples;
         const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
-        hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (+ the parked encoding's extension area)
+        if (probe) {
+            hipLaunchKernelGGL(k_mlp_gate_probe_f16, dim3(grid), dim3(512), kLdsBytesT, stream, p);
+            hipLaunchKernelGGL(k_mlp_gate_trunk_listed_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (persistent: its tile count is on the device)
+        } else {
+            hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (+ the parked encoding's extension area)
+        }
         hipLaunchKernelGGL(k_mlp_gate_heads_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);      // (persistent: its tile count is on the device)
     }
     e = hipGetLastError();
     if (e == hipSuccess && getenv("INERF_GATE_LOG")) {      // debug: the survivor share of this launch (synchronises - not for timed runs)
-        std::vector<unsigned int> h((size_t)g.n_sub);
+        std::vector<unsigned int> h((size_t)g.n_sub), hc((size_t)g.n_sub, 0u);
         e = hipStreamSynchronize(stream);
         if (e == hipSuccess) e = hipMemcpy(h.data(), counts, h.size() * 4, hipMemcpyDeviceToHost);
-        unsigned long long kept = 0;
+        if (e == hipSuccess && probe) e = hipMemcpy(hc.data(), cand_counts, hc.size() * 4, hipMemcpyDeviceToHost);
+        unsigned long long kept = 0, cand = 0;
         for (unsigned int c : h) kept += c;
-        fprintf(stderr, "inerf gate: %lld rays x %d samples in %lld sub-launches, %llu of %lld points survive (%.4f)\n", (long long)n_rays,
-                p0.n_samples, (long long)g.n_sub, kept, (long long)(n_rays * p0.n_samples), (double)kept / (double)(n_rays * p0.n_samples));
+        for (unsigned int c : hc) cand += c;
+        const double pts = (double)(n_rays * p0.n_samples);
+        fprintf(stderr, "inerf gate: %lld rays x %d samples in %lld sub-launches, %llu of %lld points survive (%.4f)", (long long)n_rays,
+                p0.n_samples, (long long)g.n_sub, kept, (long long)(n_rays * p0.n_samples), (double)kept / pts);
+        if (probe) fprintf(stderr, ", %llu are the probe's candidates (%.4f)", cand, (double)cand / pts);
+        fprintf(stderr, "\n");
     }
     return record(e);
 }

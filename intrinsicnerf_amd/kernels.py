@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _capi
-from ._capi import (BASE_CHANNELS, ENDPOINT_DIM, FLAG_ENDPOINT, FLAG_GATE_COLOUR, FLAG_LINDISP, FLAG_U_PER_RAY, FLAG_WHITE_BKGD,
+from ._capi import (BASE_CHANNELS, ENDPOINT_DIM, FLAG_ENDPOINT, FLAG_GATE_COLOUR, FLAG_GATE_PROBE, FLAG_LINDISP, FLAG_U_PER_RAY, FLAG_WHITE_BKGD,
                     RAY_FLOATS, CompositeOut, RenderArgs)
 
 MAX_POINTS_PER_LAUNCH = (1 << 31) - 1
@@ -399,16 +399,19 @@ def with_f32_fallback(desc, run):
         return run(d32)
 
 
-def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_colour=False, status_rays=0):
+def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_colour=False, status_rays=0, gate_probe=False, probe_out=None):
     """raw[N,S,CH]: fused encoding + MLP (run_network + NeRF.forward).
 
     ``status``: optional int32[1] device tensor that collects INERF_STATUS_* bits (PREC_F16X3 range check); with ``status_rays`` > 0
-    one word per that many rays.  ``gate_colour``: INERF_FLAG_GATE_COLOUR (include/inerf.h) - rows with sigma <= 0 carry zero colours."""
+    one word per that many rays.  ``gate_colour``: INERF_FLAG_GATE_COLOUR (include/inerf.h) - rows with sigma <= 0 carry zero colours.
+    ``gate_probe``: INERF_FLAG_GATE_PROBE on top of it; ``probe_out`` (tests): a float32 [N * S, 2] device tensor for the probe's (s, S)."""
     rays = _dev(rays, "rays", (None, RAY_FLOATS))
     z_vals = _dev(z_vals, "z_vals", (rays.shape[0], None))
     packed = _dev(packed, "packed weights", (None,))
     n, s = z_vals.shape
-    flags = (FLAG_ENDPOINT if endpoint else 0) | (FLAG_GATE_COLOUR if gate_colour else 0)
+    flags = (FLAG_ENDPOINT if endpoint else 0) | (FLAG_GATE_COLOUR if gate_colour else 0) | (FLAG_GATE_PROBE if gate_probe else 0)
+    if probe_out is not None:
+        probe_out = _dev(probe_out, "probe_out", (z_vals.shape[0] * z_vals.shape[1], 2))
     ch = _capi.lib().inerf_raw_channels(desc, flags, 1)
     raw = _new(rays, n, s, ch)
     with torch.cuda.device(rays.device):
@@ -416,10 +419,11 @@ def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_col
         if ws_bytes < 0:
             _capi.check(ws_bytes, "inerf_encode_mlp_workspace_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=rays.device) if ws_bytes > 0 else None
-        rc = _capi.lib().inerf_encode_mlp_chunked(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
-                                                  None if status is None else C.c_void_p(status.data_ptr()), int(status_rays),
-                                                  None if ws is None else C.c_void_p(ws.data_ptr()), ws_bytes, _stream(rays))
-    _capi.check(rc, "inerf_encode_mlp_chunked")
+        rc = _capi.lib().inerf_encode_mlp_probed(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
+                                                 None if status is None else C.c_void_p(status.data_ptr()), int(status_rays),
+                                                 None if ws is None else C.c_void_p(ws.data_ptr()), ws_bytes,
+                                                 None if probe_out is None else C.c_void_p(probe_out.data_ptr()), _stream(rays))
+    _capi.check(rc, "inerf_encode_mlp_probed")
     return raw
 
 
