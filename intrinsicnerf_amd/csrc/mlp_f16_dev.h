@@ -146,7 +146,8 @@ __device__ __forceinline__ void wide_prefetch_h(WidePreH<RB>& pre, const WeightB
 // PEEL: the first four k-blocks stand in front of the loop and, with ZERO, the first product of every accumulator takes a zero C operand (an
 // inline constant) instead of 16 * RB * PB v_mov in front of the GEMM - exposed instructions: the matrix pipe is empty until they are through.
 // NPROD: 3 - the split product hi*hi + hi*lo + lo*hi; 1 - hi*hi alone (the density gate's probe, mlp_f16_t128.hip): neither the lo plane
-// nor the lo weight fragments are read, `xl` may point into either plane.
+// nor the lo weight fragments are read, `xl` may point into either plane.  With RB = 2 and PB = 4 (one-product form only): the 64-channel x
+// 128-point wave tile of the two-workgroup probe (mlp_f16_probe.h), 128 accumulator registers.
 template <int RB, int KB0, int KB1, int ROW = kRowH, int PLANE = kPlaneH, bool ZERO = true, int KSTRIDE = RB * 2048, int PB = 2, int RBSTRIDE = 2048,
           bool PEEL = false, int NPROD = 3>
 __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const WeightBuf& wb, int frag_bytes,
@@ -154,8 +155,8 @@ __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const Weigh
                                             int col0, int col1, int lane, f32x16 (&am)[RB][PB]) {
     constexpr int KBT = KB0 + KB1;
     static_assert(KBT % 2 == 0 && KBT >= 4, "k-block count");
-    static_assert(PB == 2 || (PB == 1 && RB == 2) || (PB == 4 && RB == 1), "point blocks");
-    static_assert(NPROD == 3 || (NPROD == 1 && PB == 4 && RB == 1), "the one-product form is the 128-point tile's");
+    static_assert(PB == 2 || (PB == 1 && RB == 2) || (PB == 4 && RB == 1) || (PB == 4 && RB == 2 && NPROD == 1), "point blocks");
+    static_assert(NPROD == 3 || (NPROD == 1 && PB == 4 && (RB == 1 || RB == 2)), "the one-product form is the 128-point tile's");
     constexpr int NP = NPROD == 1 ? 1 : 2;      // operand planes / weight parts read
     if constexpr (ZERO && !PEEL) {
 #pragma unroll
@@ -223,7 +224,17 @@ __device__ __forceinline__ void wide_gemm_h(const WidePreH<RB>& pre, const Weigh
         /* issue order (masks: 0x8 MFMA, 0x20 VMEM read, 0x100 DS read).  PB = 2: MFMA, global load, MFMA, LDS read(s), MFMA - 2*RB  \
            times; PB = 1 (RB = 2: 6 MFMAs, 4 global loads, 2 LDS reads): MFMA, global load, MFMA, global load, MFMA, LDS read - twice; \
            PB = 4 (RB = 1, the 128-point tile: 12 MFMAs, 2 global loads, 8 LDS reads): the LDS reads (needed one step ahead) first */ \
-        if constexpr (NPROD == 1) {     /* 4 MFMAs, 4 LDS reads, 1 global load */                                    \
+        if constexpr (NPROD == 1 && RB == 2) {     /* (mlp_f16_probe.h) 8 MFMAs, 4 LDS reads, 2 global loads */      \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                         \
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                                   \
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   \
+            }                                                                                                        \
+        } else if constexpr (NPROD == 1) {     /* 4 MFMAs, 4 LDS reads, 1 global load */                             \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                                       \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                       \

@@ -860,6 +860,10 @@ __global__ __launch_bounds__(512, 2) void k_mlp_gate_heads_f16x3(const MlpParams
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_probe_f16(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateProbe>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_listed_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk, true>(p); }
 
+}  // namespace inerf
+#include "mlp_f16_probe.h"      // k_mlp_gate_probe_wg2_f16: the probe as two four-wave workgroups per CU
+namespace inerf {
+
 // ---- the density gate's launcher ----
 // A launch is walked in sub-ranges of whole rays, each as trunk kernel then heads kernel on the same stream (with the probe: probe kernel,
 // listed trunk, heads; the candidate list holds one index per point of a sub-range, so it cannot overflow either).  The record buffer holds one
@@ -910,9 +914,13 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_heads_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_probe_f16), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_listed_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_probe_wg2_f16), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesProbeWg2);
         if (e != hipSuccess) return record(e);
         attr_set.mark();
     }
+    // the probe's form: two four-wave workgroups per CU (mlp_f16_probe.h); INERF_PROBE_WG=1: the eight-wave workgroup (the same bits)
+    const char* const wg_env = getenv("INERF_PROBE_WG");
+    const bool probe_wg2 = !(wg_env && wg_env[0] == '1');
     for (int64_t s = 0; s < g.n_sub; ++s) {
         const int64_t r0 = s * g.rays_per_sub, nr = n_rays - r0 < g.rays_per_sub ? n_rays - r0 : g.rays_per_sub;
         MlpParams p = p0;
@@ -930,7 +938,12 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         if (p.probe_out) p.probe_out = p0.probe_out + 2 * r0 * p0.n_samples;
         const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
         if (probe) {
-            hipLaunchKernelGGL(k_mlp_gate_probe_f16, dim3(grid), dim3(512), kLdsBytesT, stream, p);
+            if (probe_wg2) {
+                const int grid2 = p.n_tiles < 2 * device_cus() ? p.n_tiles : 2 * device_cus();
+                hipLaunchKernelGGL(k_mlp_gate_probe_wg2_f16, dim3(grid2), dim3(kProbeWg2Threads), kLdsBytesProbeWg2, stream, p);
+            } else {
+                hipLaunchKernelGGL(k_mlp_gate_probe_f16, dim3(grid), dim3(512), kLdsBytesT, stream, p);
+            }
             hipLaunchKernelGGL(k_mlp_gate_trunk_listed_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (persistent: its tile count is on the device)
         } else {
             hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (+ the parked encoding's extension area)
