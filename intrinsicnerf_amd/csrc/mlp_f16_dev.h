@@ -79,6 +79,13 @@ __device__ __forceinline__ void hi_store_parked(_Float16* hi_ptr, float v, float
     amax = fmaxf(amax, fabsf(t));
 }
 
+// ... and the hi plane alone (the probe as two workgroups per CU: its tile has no lo plane): hi_store_parked's value and maximum.
+__device__ __forceinline__ void hi_store(_Float16* hi_ptr, float v, float& amax) {
+    const float t = v * kActScale;
+    hi_ptr[0] = (_Float16)t;
+    amax = fmaxf(amax, fabsf(t));
+}
+
 // sin and cos of an encoding argument a = x * 2^f (|a| up to 6 * 2^9 on the chair scene, 2^9 on the room's x / 10).
 // ocml's sincosf spends ~100 instructions (and diverges into its large-argument path) per call; the encodings are 24
 // calls per sample point.  This is the classic three-constant Cody-Waite reduction, exact to ~6e-8 in the reduced

@@ -36,11 +36,8 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
     wb.voff = (tid & 63) * 16;
     // this wave's 64-channel stream of a 256-wide layer: packing wave `wave`, k-blocks 4 KiB apart, row blocks 2 KiB apart (hi fragments alone)
     auto frag64 = [&](const GemmSlot& s, int kbt) { return (s.w + wave * kbt * 2 * 2 * 256) * 4; };
-    auto pad_of = [&](int r) { return reinterpret_cast<int*>(ldst + r * kRowD + kWidth + kDirCols); };
-
     WidePreH<2> pre;
-    auto pf = [&](const GemmSlot& s, int kbt, int kb_first) { prefetch_w<2, 4096, 2048, 1>(pre, wb, frag64(s, kbt) + kb_first * 4096); };
-    pf(L.trunk[0], 4, 0);
+    prefetch_w<2, 4096, 2048, 1>(pre, wb, frag64(L.trunk[0], 4));
 
     for (int tile = blockIdx.x; tile < p.n_tiles; tile += gridDim.x) {
         int lane_t = tid;                         // (laundered per tile, like the eight-wave form's)
@@ -58,91 +55,18 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
             const int ray = gp / p.n_samples;
             const float* __restrict__ r = p.rays + (size_t)ray * INERF_RAY_FLOATS;
             _Float16* row = ldst + pt * kRowD;
-            const float zz = __builtin_nontemporal_load(p.z + gp);
-            float x[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));      // run_nerf.py:488
-            auto hi_store = [&](_Float16* dst, float v) {      // hi_store_parked's value and maximum, the plane alone
-                const float t = v * kActScale;
-                dst[0] = (_Float16)t;
-                amax = fmaxf(amax, fabsf(t));
-            };
-            for (int f = part; f < p.l_xyz; f += kParts) {
-                const float s = (float)(1 << f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sn, cs;
-                    fast_sincosf(x[c] * s, &sn, &cs);
-                    hi_store(row + 3 + 6 * f + c, sn);
-                    hi_store(row + 6 + 6 * f + c, cs);
-                }
-            }
-            if (part == kParts - 1) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) hi_store(row + c, x[c]);
-                for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) row[c] = (_Float16)0.0f;
-            }
+            encode_position<false, kParts, kParts - 1, &hi_store, 0>(p, r, gp, part, row, amax);
         }
         __syncthreads();
-        // the encoding parked for the skip layer before layer 0's epilogue overwrites it (every wave's copy is read in front of that
-        // layer's first barrier): a thread parks and restores the SAME four pieces - piece j = tid & 7 of rows tid >> 3 + 32 i - so the
-        // parked copy needs no barrier of its own.  The pad words it covers hold the candidate counts only behind layer 7.
-        auto park_copy = [&](bool restore) {
-            int t = tid;
-            asm volatile("" : "+v"(t));
-            const int r = t >> 3, j = t & 7;
-            const bool in_row = j < kParkRowPieces;
-            _Float16* const cols = ldst + r * kRowD + j * 8;
-            _Float16* const parked = in_row ? cols + kColDirD : ldst + kPlaneT + (r * kParkExtPieces + (j - kParkRowPieces)) * 8;
-            u32x4 v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const _Float16* const a = cols + i * 32 * kRowD;
-                const _Float16* const b = parked + (in_row ? i * 32 * kRowD : i * 32 * kParkExtPieces * 8);
-                v[i] = *reinterpret_cast<const u32x4*>(restore ? b : a);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                _Float16* const a = cols + i * 32 * kRowD;
-                _Float16* const b = parked + (in_row ? i * 32 * kRowD : i * 32 * kParkExtPieces * 8);
-                *reinterpret_cast<u32x4*>(restore ? a : b) = v[i];
-            }
-        };
-        park_copy(false);
+        park_encoding<1, kProbeWg2Threads>(ldst, tid, false);      // (before layer 0's epilogue overwrites the encoding)
 
-        // ---------------- trunk: one product per MAC, the hi plane in place ----------------
-        f32x16 am[2][4];
-        f32x4 bias[2][4];
-        float inv;
-        auto store_hi = [&](const GemmSlot& s, const GemmSlot& next, int kbt, int kb_first) {
-            load_bias<2>(bias, inv, wb, (s.b + 64 * wave) * 4, (s.b + kWidth) * 4, lane_t);
-            pf(next, kbt, kb_first);
-            __syncthreads();                       // every wave has read the layer's input
-            wide_store_h<2, kRowD, kPlaneT, false, false, 4, true, true>(am, inv, bias, xd, true, amax2, nullptr, 0, 0, 0);
-            __syncthreads();
-        };
-        wide_gemm_h<2, 4, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre, wb, frag64(L.trunk[0], 4), xr, 0, 0, lane_t, am);
-        store_hi(L.trunk[0], L.trunk[1], 16, 0);
-#pragma unroll 1
-        for (int layer = 1; layer < kSkipInput; ++layer) {
-            wide_gemm_h<2, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre, wb, frag64(L.trunk[layer], 16), xr, 0, 0, lane_t, am);
-            if (layer + 1 < kSkipInput) store_hi(L.trunk[layer], L.trunk[layer + 1], 16, 0);
-            else                        store_hi(L.trunk[layer], L.trunk[kSkipInput], 20, 4);
-        }
-        {   // pts_linears[5] over cat([pts, h]): the h part (k-blocks 4..19 of the stream), then the encoding back in columns 0..63
-            const GemmSlot& s = L.trunk[kSkipInput];
-            wide_gemm_h<2, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre, wb, frag64(s, 20) + 4 * 4096, xr, 0, 0, lane_t, am);
-            pf(s, 20, 0);
+        // ---------------- trunk: the skip layer's encoding back in columns 0..63 between two barriers ----------------
+        probe_trunk<2>(pre, wb, L, frag64, xr, xd, wave, lane_t, amax2, [&]() {
             __syncthreads();                       // every wave has read h4
-            park_copy(true);
+            park_encoding<1, kProbeWg2Threads>(ldst, tid, true);
             __syncthreads();
-            wide_gemm_h<2, 4, 0, kRowD, kPlaneT, false, 4096, 4, 2048, false, 1>(pre, wb, frag64(s, 20), xr, 0, 0, lane_t, am);
-            store_hi(s, L.trunk[6], 16, 0);
-        }
-        wide_gemm_h<2, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre, wb, frag64(L.trunk[6], 16), xr, 0, 0, lane_t, am);
-        store_hi(L.trunk[6], L.trunk[7], 16, 0);
-        wide_gemm_h<2, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre, wb, frag64(L.trunk[7], 16), xr, 0, 0, lane_t, am);
-        store_hi(L.trunk[7], L.trunk[0], 4, 0);
+            return xr;
+        });
 
         // ---------------- s and S, the raw rows, the candidate list: this wave's 32 points as two groups of 16 ----------------
         // (group 2 wave + h is wave 2 wave + h of the eight-wave form: the same counts in the same pad words, the list in point order)
@@ -157,48 +81,17 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
             const bool valid = lane_t < 16 && pt16 + lane_t < p.n_points;
             keep[h] = valid && !(sigma < -kProbeKappa * scale);
             kept[h] = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep[h]));
-            // raw: the group's 16 points x 11 floats as 44 sixteen-byte pieces (like the whole kernel's), s in channel 3 of zeros
-            float piece[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int e = 4 * (lane_t < 44 ? lane_t : 43) + i, pt = e / INERF_BASE_CHANNELS;
-                const float s_pt = __shfl(sigma, pt);
-                piece[i] = e - INERF_BASE_CHANNELS * pt == 3 ? s_pt : 0.0f;
-            }
-            if (p.channels == INERF_BASE_CHANNELS && pt16 + 16 <= p.n_points && (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0) {
-                if (lane_t < 44)
-                    __builtin_nontemporal_store(f32x4{piece[0], piece[1], piece[2], piece[3]},
-                                                reinterpret_cast<f32x4*>(p.raw + (size_t)pt16 * INERF_BASE_CHANNELS) + lane_t);
-            } else if (valid) {
-                float* const out_row = p.raw + (size_t)(pt16 + lane_t) * p.channels;
-#pragma unroll
-                for (int c = 0; c < INERF_BASE_CHANNELS; ++c) __builtin_nontemporal_store(c == 3 ? sigma : 0.0f, out_row + c);
-            }
+            store_sigma_rows(p, pt16, sigma, lane_t);
             if (p.probe_out && valid) {            // tests: (s, S) per point
                 p.probe_out[2 * (size_t)(pt16 + lane_t)] = sigma;
                 p.probe_out[2 * (size_t)(pt16 + lane_t) + 1] = scale;
             }
         }
-        if (lane_t == 0) {
-            pad_of(2 * wave)[0] = __popc(kept[0]);
-            pad_of(2 * wave + 1)[0] = __popc(kept[1]);
-        }
-        __syncthreads();                           // the eight counts are there
-        int before = 0, total = 0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const int c = pad_of(g)[0];
-            total += c;
-            before += g < 2 * wave ? c : 0;
-        }
-        if (tid == 0) pad_of(8)[0] = total > 0 ? (int)atomicAdd(p.cand_count, (unsigned)total) : 0;
-        __syncthreads();
-        // (<= the launch's points - this wave's candidates: inside the list)
-        const int slot0 = __builtin_amdgcn_readfirstlane(pad_of(8)[0] + before);
-        const int slot1 = slot0 + __popc(kept[0]);
+        post_count(ldst, 2 * wave, kept[0], lane_t);         // (behind both groups' rows: posted per group in the loop the frame takes 0.5 ms
+        post_count(ldst, 2 * wave + 1, kept[1], lane_t);     // longer - profiles/gate_dedup_bench.txt)
         const int pt32 = tile * kPtsT + 32 * wave;
-        if (keep[0]) p.cand_idx[slot0 + __popc(kept[0] & ((1u << lane_t) - 1u))] = pt32 + lane_t;
-        if (keep[1]) p.cand_idx[slot1 + __popc(kept[1] & ((1u << lane_t) - 1u))] = pt32 + 16 + lane_t;
+        const int point[2] = {pt32 + lane_t, pt32 + 16 + lane_t};
+        reserve_slots<2>(ldst, p.cand_count, p.cand_idx, keep, kept, point, wave, lane_t, tid);
         flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
         __syncthreads();                           // the rows and the pad words are read: the next tile's encode and parking may overwrite them
     }

@@ -104,6 +104,10 @@ constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
 // The probe's margin: the smallest power of two >= 8 x the largest |s - sigma| / S measured on the GPU (profiles/gate_probe_margin.txt).
 constexpr float kProbeKappa = 0x1p-6f;
 
+}  // namespace inerf
+#include "mlp_f16_gate.h"       // the pieces the gate's kernels share: encoder, parking, probe trunk, raw rows, slots
+namespace inerf {
+
 template <bool kSsr, bool kSave, bool kPipe, int kMode, bool kListed = false>
 __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     static_assert(!(kSsr && kSave), "the saving form is the object-level network's");
@@ -150,9 +154,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         n_rec = n_rec < p.n_points ? n_rec : p.n_points;
     }
     const int n_tiles = kMode == kGateHeads || kListed ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
-    // the 16 pad bytes behind a row's direction columns (hi plane; no GEMM uses what it reads there).  Gated trunk: rows 0..7 hold the
-    // waves' survivor counts, row 8 the tile's first record.  Gated heads: row r holds four words, non-zero when point r left the f16 range
-    auto pad_of = [&](int r) { return reinterpret_cast<int*>(ldst + r * kRowD + kWidth + kDirCols); };
+    auto pad_of = [&](int r) { return pad_words(ldst, r); };      // (gated heads: the point's range flags)
     float amax = 0.0f;                            // running maxima of |scaled value| (encoder inputs / layer outputs): the f16 range guard
     f16x2 amax2 = {(_Float16)0.0f, (_Float16)0.0f};
     const int n_tiles64 = (p.n_points + kTilePoints - 1) / kTilePoints;      // the save slots' tiles
@@ -179,38 +181,9 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             const int ray = gp / n_samples;
             const float* __restrict__ r = p.rays + (size_t)ray * INERF_RAY_FLOATS;
             _Float16* row = ldst + pt * kRowD;
-            if constexpr (kMode != kGateHeads) {      // (the gated heads' rows arrive with h7 in these columns)
-                const float zz = __builtin_nontemporal_load(p.z + gp);
-                float x[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));                                // run_nerf.py:488
-                    if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);              // semantic_nerf.py:64
-                }
-                for (int f = part; f < p.l_xyz; f += kParts) {
-                    const float s = (float)(1 << f);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float sn, cs;
-                        fast_sincosf(x[c] * s, &sn, &cs);
-                        if constexpr (kMode == kGateProbe) {
-                            hi_store_parked<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
-                            hi_store_parked<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
-                        } else {
-                            split_store<kPlaneT>(row + 3 + 6 * f + c, sn, amax);
-                            split_store<kPlaneT>(row + 6 + 6 * f + c, cs, amax);
-                        }
-                    }
-                }
-                if (part == 2) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        if constexpr (kMode == kGateProbe) hi_store_parked<kPlaneT>(row + c, x[c], amax);
-                        else                               split_store<kPlaneT>(row + c, x[c], amax);
-                    }
-                    for (int c = 3 + 6 * p.l_xyz; c < kEncCols; ++c) { row[c] = (_Float16)0.0f; row[kPlaneT + c] = (_Float16)0.0f; }
-                }
-            }
+            constexpr auto kStore = kMode == kGateProbe ? &hi_store_parked<kPlaneT> : &split_store<kPlaneT>;
+            if constexpr (kMode != kGateHeads)        // (the gated heads' rows arrive with h7 in these columns)
+                encode_position<kSsr, kParts, 2, kStore, kPlaneT>(p, r, gp, part, row, amax);
             if constexpr (kMode != kGateTrunk && kMode != kGateProbe) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
                 const int fd = kParts - 1 - part;
                 if (fd < p.l_dir) {
@@ -269,38 +242,12 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                                                            (int)blockIdx.x * kEncCacheBytesT + (tid + 512 * i) * 16, 0, 0);
             }
         }
-        // gated trunk: the same pieces parked in LDS (kParkRowPieces above) before layer 0's epilogue overwrites them - every wave's copy
-        // is read in front of that layer's first barrier; a thread parks and restores the SAME four pieces (piece j = tid & 7 of rows
-        // tid >> 3 and + 64 of both planes), so the parked copy needs no barrier of its own.  The pad words it covers hold the survivor
-        // counts only behind layer 7.  (Addresses from a laundered index, rebuilt at the skip layer instead of held across five layers.)
+        // gated trunk: the same pieces parked in LDS (park_encoding, mlp_f16_gate.h)
         constexpr bool kPark = kMode == kGateTrunk && INERF_GATE_TRUNK_PARK;
-        auto park_copy = [&](bool restore) {
-            int t = tid;
-            asm volatile("" : "+v"(t));
-            const int r = t >> 3, j = t & 7;
-            const bool in_row = j < kParkRowPieces;
-            _Float16* const cols = ldst + r * kRowD + j * 8;
-            _Float16* const parked = in_row ? cols + kColDirD : ldst + 2 * kPlaneT + (r * kParkExtPieces + (j - kParkRowPieces)) * 8;
-            u32x4 v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int at_cols = (i >> 1) * kPlaneT + (i & 1) * 64 * kRowD;
-                const _Float16* const a = cols + at_cols;
-                const _Float16* const b = parked + (in_row ? at_cols : i * 64 * kParkExtPieces * 8);
-                v[i] = *reinterpret_cast<const u32x4*>(restore ? b : a);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int at_cols = (i >> 1) * kPlaneT + (i & 1) * 64 * kRowD;
-                _Float16* const a = cols + at_cols;
-                _Float16* const b = parked + (in_row ? at_cols : i * 64 * kParkExtPieces * 8);
-                *reinterpret_cast<u32x4*>(restore ? a : b) = v[i];
-            }
-        };
-        if constexpr (kPark) park_copy(false);
+        if constexpr (kPark) park_encoding<2, 512>(ldst, tid, false);
         auto encode_again = [&]() {         // the encoding back into columns 0..63 (sc0: past the vector L1, whose lines of an earlier tile may be stale)
             if constexpr (kPark) {
-                park_copy(true);
+                park_encoding<2, 512>(ldst, tid, true);
                 return;
             }
             if constexpr (!kSsr && !kSave) {
@@ -437,34 +384,8 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             pp_epilogue<kRowD, kPlaneT>(accB, inv, bias[0], xdB, amax2);      // E(7,B): nothing left to run it under
             __syncthreads();
         } else if constexpr (kMode == kGateProbe) {
-            // one product per MAC: the hi plane in place, the skip layer's encoding from its copy in the lo plane (nothing overwrites it)
-            auto pf1 = [&](const GemmSlot& s, int kbt, int kb_first) { prefetch_w<1, 4096, 2048, 1>(pre1, wb, frag32(s, kbt) + kb_first * 4096); };
-            auto store_hi = [&](const GemmSlot& s, const GemmSlot& next, int kbt, int kb_first) {
-                load_bias<1>(bias1, inv1, wb, (s.b + 32 * wave) * 4, (s.b + kWidth) * 4, lane_t);
-                pf1(next, kbt, kb_first);
-                __syncthreads();                       // every wave has read the layer's input
-                wide_store_h<1, kRowD, kPlaneT, false, false, 4, true, true>(am1, inv1, bias1, xd, true, amax2, nullptr, 0, 0, 0);
-                __syncthreads();
-            };
-            wide_gemm_h<1, 4, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[0], 4), xr, 0, 0, lane_t, am1);
-            store_hi(L.trunk[0], L.trunk[1], 16, 0);
-    #pragma unroll 1
-            for (int layer = 1; layer < kSkipInput; ++layer) {
-                wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[layer], 16), xr, 0, 0, lane_t, am1);
-                if (layer + 1 < kSkipInput) store_hi(L.trunk[layer], L.trunk[layer + 1], 16, 0);
-                else                        store_hi(L.trunk[layer], L.trunk[kSkipInput], 20, 4);
-            }
-            {
-                const GemmSlot& s = L.trunk[kSkipInput];
-                wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(s, 20) + 4 * 4096, xr, 0, 0, lane_t, am1);
-                pf1(s, 20, 0);
-                wide_gemm_h<1, 4, 0, kRowD, kPlaneT, false, 4096, 4, 2048, false, 1>(pre1, wb, frag32(s, 20), xr + kPlaneT, 0, 0, lane_t, am1);
-                store_hi(s, L.trunk[6], 16, 0);
-            }
-            wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[6], 16), xr, 0, 0, lane_t, am1);
-            store_hi(L.trunk[6], L.trunk[7], 16, 0);
-            wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, true, 1>(pre1, wb, frag32(L.trunk[7], 16), xr, 0, 0, lane_t, am1);
-            store_hi(L.trunk[7], L.trunk[0], 4, 0);
+            // the skip layer's encoding from its copy in the lo plane (nothing overwrites it)
+            probe_trunk<1>(pre1, wb, L, frag32, xr, xd, wave, lane_t, amax2, [&]() { return xr + kPlaneT; });
         } else {
             wide_gemm_h<1, 4, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[0], 4), xr, 0, 0, lane_t, am1);
             store256(L.trunk[0], true, SAVE_H0, pf32(L.trunk[1], 16), kWithBits);
@@ -491,110 +412,34 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             else                               store256(L.trunk[7], true, SAVE_H7, pf256(L.as1, 16), kWithBits);
         }
 
-        // ---------------- density gate: sigma, the raw rows, the survivors' records ----------------
-        if constexpr (kMode == kGateTrunk && !kListed) {
-            const int pt16 = tile * kPtsT + 16 * wave;
-            const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
-            const float sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];   // lanes 0..15: this wave's points
-            const bool keep = lane_t < 16 && pt16 + lane_t < p.n_points && !(sigma <= 0.0f);
-            const unsigned kept = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep));
-            if (lane_t == 0) pad_of(wave)[0] = __popc(kept);
-            // raw: the wave's 16 points x 11 floats as 44 sixteen-byte pieces (like the whole kernel's), sigma in channel 3 of zeros
-            float piece[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int e = 4 * (lane_t < 44 ? lane_t : 43) + i, pt = e / INERF_BASE_CHANNELS;
-                const float s_pt = __shfl(sigma, pt);
-                piece[i] = e - INERF_BASE_CHANNELS * pt == 3 ? s_pt : 0.0f;
-            }
-            if (p.channels == INERF_BASE_CHANNELS && pt16 + 16 <= p.n_points && (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0) {
-                if (lane_t < 44)
-                    __builtin_nontemporal_store(f32x4{piece[0], piece[1], piece[2], piece[3]},
-                                                reinterpret_cast<f32x4*>(p.raw + (size_t)pt16 * INERF_BASE_CHANNELS) + lane_t);
-            } else if (lane_t < 16 && pt16 + lane_t < p.n_points) {
-                float* const out_row = p.raw + (size_t)(pt16 + lane_t) * p.channels;
-#pragma unroll
-                for (int c = 0; c < INERF_BASE_CHANNELS; ++c) __builtin_nontemporal_store(c == 3 ? sigma : 0.0f, out_row + c);
-            }
-            __syncthreads();                       // the eight counts are there
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) {
-                const int c = pad_of(w)[0];
-                total += c;
-                before += w < wave ? c : 0;
-            }
-            if (tid == 0) pad_of(8)[0] = total > 0 ? (int)atomicAdd(p.gate_count, (unsigned)total) : 0;
-            __syncthreads();
-            const int slot0 = __builtin_amdgcn_readfirstlane(pad_of(8)[0] + before);      // (<= the launch's points - this wave's survivors: inside the buffers)
-            if (keep) p.gate_idx[slot0 + __popc(kept & ((1u << lane_t) - 1u))] = pt16 + lane_t;
-            int slot = slot0;
-            for (unsigned m = kept; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
-                const int j = __builtin_ctz(m);
-                const u32x4 v = *reinterpret_cast<const u32x4*>(ldst + (lane_t >> 5) * kPlaneT + (16 * wave + j) * kRowD + 8 * (lane_t & 31));
-                __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p.gate_rec + (size_t)slot * kGateRecordBytes) + lane_t);
-            }
-            flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
-            __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
-            continue;
-        }
-
-        // ---------------- the same for the probe (s and S, the raw rows, the candidate list) and the listed trunk (sigma scattered, records) ----------------
-        if constexpr (kListed || kMode == kGateProbe) {
+        // ---------------- density gate: sigma (probe: s and S), the raw rows, the survivors' records or the candidate list ----------------
+        if constexpr (kMode == kGateTrunk || kMode == kGateProbe) {
             const int pt16 = tile * kPtsT + 16 * wave;
             const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
             float sigma, scale = 0.0f;                 // lanes 0..15: this wave's points
             if constexpr (kMode == kGateProbe) skinny_probe_h<8>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t, sigma, scale);
             else sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];
             const bool valid = lane_t < 16 && pt16 + lane_t < (kListed ? n_rec : p.n_points);
-            const bool keep = valid && (kMode == kGateProbe ? !(sigma < -kProbeKappa * scale) : !(sigma <= 0.0f));
-            const unsigned kept = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep));
-            if (lane_t == 0) pad_of(wave)[0] = __popc(kept);
-            int my_point = pt16 + lane_t;              // the row's point within the sub-range
+            const bool keep[1] = {valid && (kMode == kGateProbe ? !(sigma < -kProbeKappa * scale) : !(sigma <= 0.0f))};
+            const unsigned kept[1] = {(unsigned)__builtin_amdgcn_readfirstlane((unsigned)__ballot(keep[0]))};
+            post_count(ldst, wave, kept[0], lane_t);
+            int my_point[1] = {pt16 + lane_t};         // the row's point within the sub-range
             if constexpr (kListed) {                   // exact sigma into the candidate's raw row, whose other ten channels the probe zeroed
-                my_point = p.cand_idx[valid ? pt16 + lane_t : 0];
-                if (valid) __builtin_nontemporal_store(sigma, p.raw + (size_t)my_point * p.channels + 3);
+                my_point[0] = p.cand_idx[valid ? pt16 + lane_t : 0];
+                if (valid) __builtin_nontemporal_store(sigma, p.raw + (size_t)my_point[0] * p.channels + 3);
             } else {
-                // raw: the wave's 16 points x 11 floats as 44 sixteen-byte pieces (like the whole kernel's), sigma in channel 3 of zeros
-                float piece[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int e = 4 * (lane_t < 44 ? lane_t : 43) + i, pt = e / INERF_BASE_CHANNELS;
-                    const float s_pt = __shfl(sigma, pt);
-                    piece[i] = e - INERF_BASE_CHANNELS * pt == 3 ? s_pt : 0.0f;
-                }
-                if (p.channels == INERF_BASE_CHANNELS && pt16 + 16 <= p.n_points && (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0) {
-                    if (lane_t < 44)
-                        __builtin_nontemporal_store(f32x4{piece[0], piece[1], piece[2], piece[3]},
-                                                    reinterpret_cast<f32x4*>(p.raw + (size_t)pt16 * INERF_BASE_CHANNELS) + lane_t);
-                } else if (lane_t < 16 && pt16 + lane_t < p.n_points) {
-                    float* const out_row = p.raw + (size_t)(pt16 + lane_t) * p.channels;
-#pragma unroll
-                    for (int c = 0; c < INERF_BASE_CHANNELS; ++c) __builtin_nontemporal_store(c == 3 ? sigma : 0.0f, out_row + c);
-                }
+                store_sigma_rows(p, pt16, sigma, lane_t);
             }
             if constexpr (kMode == kGateProbe)
                 if (p.probe_out && valid) {            // tests: (s, S) per point
                     p.probe_out[2 * (size_t)(pt16 + lane_t)] = sigma;
                     p.probe_out[2 * (size_t)(pt16 + lane_t) + 1] = scale;
                 }
-            __syncthreads();                       // the eight counts are there
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) {
-                const int c = pad_of(w)[0];
-                total += c;
-                before += w < wave ? c : 0;
-            }
-            unsigned int* const counter = kMode == kGateProbe ? p.cand_count : p.gate_count;
-            int* const index_list = kMode == kGateProbe ? p.cand_idx : p.gate_idx;
-            if (tid == 0) pad_of(8)[0] = total > 0 ? (int)atomicAdd(counter, (unsigned)total) : 0;
-            __syncthreads();
-            const int slot0 = __builtin_amdgcn_readfirstlane(pad_of(8)[0] + before);      // (<= the launch's points - this wave's survivors: inside the buffers)
-            if (keep) index_list[slot0 + __popc(kept & ((1u << lane_t) - 1u))] = my_point;
+            const int slot0 = reserve_slots<1>(ldst, kMode == kGateProbe ? p.cand_count : p.gate_count, kMode == kGateProbe ? p.cand_idx : p.gate_idx,
+                                               keep, kept, my_point, wave, lane_t, tid);
             if constexpr (kMode == kGateTrunk) {
                 int slot = slot0;
-                for (unsigned m = kept; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
+                for (unsigned m = kept[0]; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
                     const int j = __builtin_ctz(m);
                     const u32x4 v = *reinterpret_cast<const u32x4*>(ldst + (lane_t >> 5) * kPlaneT + (16 * wave + j) * kRowD + 8 * (lane_t & 31));
                     __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p.gate_rec + (size_t)slot * kGateRecordBytes) + lane_t);
@@ -910,12 +755,13 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
     if (e != hipSuccess) return record(e);
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_heads_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_probe_f16), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesT);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_trunk_listed_f16x3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_gate_probe_wg2_f16), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesProbeWg2);
-        if (e != hipSuccess) return record(e);
+        const struct { void (*kernel)(const MlpParams); int lds_bytes; } kernels[] = {
+            {k_mlp_gate_trunk_f16x3, kLdsBytesTrunk}, {k_mlp_gate_heads_f16x3, kLdsBytesT}, {k_mlp_gate_probe_f16, kLdsBytesT},
+            {k_mlp_gate_trunk_listed_f16x3, kLdsBytesTrunk}, {k_mlp_gate_probe_wg2_f16, kLdsBytesProbeWg2}};
+        for (const auto& k : kernels) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes);
+            if (e != hipSuccess) return record(e);
+        }
         attr_set.mark();
     }
     // the probe's form: two four-wave workgroups per CU (mlp_f16_probe.h); INERF_PROBE_WG=1: the eight-wave workgroup (the same bits)

@@ -320,9 +320,10 @@ def test_encode_mlp_raw(variant, c, s):
 @pytest.mark.parametrize("c", [5, 28, 33, 101, 240])
 def test_ssr_semantic_head_forms_agree(c, precision, monkeypatch):
     """The SSR network's two semantic-head forms of the two-workgroup kernel - per wave (every wave the whole head for its 16
-    points) and channel-split (hidden layer split over the waves, partial logits through an L2-resident scratch; the default
-    for C <= 32, forced here for every C: more than 32 classes go block by block through the exchange area) - and the opt-in
-    128-point tile (INERF_F16_KERNEL=t128, C <= 32) against the oracle and against each other: the 11 base channels bit for bit,
+    points) and channel-split (hidden layer split over the waves, partial logits through an L2-resident scratch; that kernel's default
+    for C <= 32, forced here for every C: more than 32 classes go block by block through the exchange area) - and the 128-point
+    tile, which SSR takes only with INERF_F16_KERNEL=t128 and C <= 32 (mlp_f16x3_takes_t128; the SSR default is the two-workgroup
+    kernel), against the oracle and against each other: the 11 base channels bit for bit,
     the logits up to their summation order."""
     from intrinsicnerf_amd import kernels
     if precision != "f16x3":

@@ -90,7 +90,8 @@ def test_default_inference_kernels_do_not_live_in_scratch(tmp_path):
         if "ILb0E" in k:
             assert v == 0, f"{k}: {v} bytes of scratch per lane"
     assert scratch["_ZN5inerf23k_encode_mlp_f16x3_dualILb0ELb0ELb0EEEvNS_9MlpParamsE"] == 0          # the 64-point form of the headline kernel: none
-    # the 128-point tile (round 6): the object-level headline kernel; for SSR an opt-in form (INERF_F16_KERNEL=t128, C <= 32) - none
+    # the 128-point tile (round 6): the object-level headline kernel; SSR takes it only with INERF_F16_KERNEL=t128 and C <= 32
+    # (mlp_f16x3_takes_t128: its default stays the two-workgroup kernel above) - none
     t128 = {k: v for k, v in scratch.items() if "k_encode_mlp_f16x3_t128" in k}
     # <kSsr, kSave, kPipe>: the two inference forms (object-level default, SSR opt-in) hold no scratch; the opt-in saving form
     # (INERF_TRAIN_FWD=t128) and the opt-in pipelined trunk (INERF_F16_KERNEL=pp) may keep a few dwords (at most 128 bytes per lane)
