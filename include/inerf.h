@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40016
+#define INERF_ABI_VERSION 40017
 
 /* error codes */
 #define INERF_OK              0
@@ -521,6 +521,37 @@ int inerf_render_rays_drawn(const inerf_render_args* args, const inerf_draw_args
 int inerf_gen_rays(const float* poses, int pose_stride, const float* static_poses, int n_poses, int height, int width,
                    float fx, float fy, float cx, float cy, float near, float far, uint32_t flags, float* rays_out,
                    void* stream);
+
+/* The NDC projection of forward-facing scenes (ndc_rays, run_nerf_helpers.py:381-399), as render() applies it to the origin
+ * and direction of every ray of the LLFF configs (run_nerf.py:117-119: ndc_rays(H, W, K[0][0], 1., rays_o, rays_d)).
+ *   sx = -1./(W/(2.*focal)), sy = -1./(H/(2.*focal)) (run_nerf_helpers.py:387-393, evaluated by the caller and rounded to
+ *   fp32 once, which is what ATen does with a Python scalar); near_plane = the `near` argument of ndc_rays.
+ * Every fp32 operation is issued in ATen's CPU order (csrc/frame_ops.hip): t = (-(near + o_z)) / d_z, o' = o + t d without
+ * fma, every quotient a true division, and `scalar / o'_z` as the correctly rounded reciprocal times the scalar that
+ * Tensor.__rtruediv__ evaluates.  Bit-identical to the reference's CPU rays (tests/golden/rays_generators.npz: ndc_o, ndc_d,
+ * render_rays_ndc; tests/golden/uncurated_object_llff_ndc.npz: rays). */
+typedef struct inerf_ndc { float sx, sy, near_plane; } inerf_ndc;          /* [host] */
+
+/* inerf_gen_rays with the NDC projection of run_nerf_helpers.py:381-399 applied to origin and direction
+ * (run_nerf.py:117-119); view directions stay the world-space direction of `poses` over its norm (run_nerf.py:101-108),
+ * with static_poses origin and direction - and so the NDC of them - come from the static camera; near / far are columns 6
+ * and 7 as given.  ndc == NULL: exactly inerf_gen_rays. */
+int inerf_gen_rays_ndc(const float* poses, int pose_stride, const float* static_poses, int n_poses, int height, int width,
+                       float fx, float fy, float cx, float cy, float near, float far, uint32_t flags,
+                       const inerf_ndc* ndc, float* rays_out, void* stream);
+
+/* The [n, 11] batch render() assembles from GIVEN rays (run_nerf.py:106-128; every object-level training step,
+ * run_nerf.py:942): view direction = d / |d| with |d| = sqrt(fma(d2, d2, fma(d1, d1, d0 * d0))) (torch.norm on the CPU) and
+ * a true division, optional NDC of origin and direction (ndc NULL: none), near / far columns.  rays_o / rays_d: rows of three
+ * floats, consecutive rows o_stride / d_stride (>= 3) floats apart - columns 0:3 and 3:6 of an [n, 11] batch go in as they
+ * are.  rays_out must not overlap the inputs.  INERF_E_UNSUPPORTED beyond (2^31 - 1) * 256 rays. */
+int inerf_assemble_rays(const float* rays_o, int64_t o_stride, const float* rays_d, int64_t d_stride, int64_t n_rays,
+                        float near, float far, const inerf_ndc* ndc /* or NULL */, float* rays_out, void* stream);
+
+/* ndc_rays alone (run_nerf_helpers.py:381-399): contiguous [n, 3] outputs; o_out / d_out may alias rays_o / rays_d when
+ * those are contiguous (stride 3).  ndc must not be NULL. */
+int inerf_ndc_rays(const float* rays_o, int64_t o_stride, const float* rays_d, int64_t d_stride, int64_t n_rays,
+                   const inerf_ndc* ndc, float* o_out, float* d_out, void* stream);
 
 /* to8b on the device: out[i] = (uint8)(255 * clip(values[i], 0, 1)) (run_nerf_helpers.py:13 / trainer.py:1242), so an
  * image loop (run_nerf.py:142-212, trainer.py:1221-1389) copies a quarter of the bytes to the host.  NaN -> 0. */

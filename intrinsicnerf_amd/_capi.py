@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40016          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40017          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -113,6 +113,11 @@ class DrawArgs(C.Structure):
                 ("noise_std", C.c_float), ("flags", C.c_uint32)]
 
 
+class Ndc(C.Structure):
+    """inerf_ndc: the NDC projection's coefficients (include/inerf.h, inerf_gen_rays_ndc)."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("near_plane", C.c_float)]
+
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -173,6 +178,10 @@ SYMBOLS = {
     "inerf_render_workspace_bytes": (_L, [C.POINTER(RenderArgs)]),
     "inerf_render_rays": (_I, [C.POINTER(RenderArgs), _P]),
     "inerf_gen_rays": (_I, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _U, _P, _P]),
+    "inerf_gen_rays_ndc": (_I, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _U,
+                                C.POINTER(Ndc), _P, _P]),
+    "inerf_assemble_rays": (_I, [_P, _L, _P, _L, _L, C.c_float, C.c_float, C.POINTER(Ndc), _P, _P]),
+    "inerf_ndc_rays": (_I, [_P, _L, _P, _L, _L, C.POINTER(Ndc), _P, _P, _P]),
     "inerf_frame_to_u8": (_I, [_P, _L, _P, _P]),
     "inerf_cluster_lookup": (_I, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _P]),
     "inerf_cluster_fit_workspace_bytes": (_L, [_L, _I, _L]),

@@ -5,7 +5,7 @@ image, then pull each map to the host with its own ``.cpu().numpy()`` - six bloc
 of which first waits for the whole render.  Here a frame's maps are packed into ONE device tensor, copied into one of two
 pinned host buffers on a side stream, and the next frame's kernels are enqueued while that copy runs; the host touches a
 frame only when the frame after it has been enqueued.  ``to8b`` happens on the device when only 8-bit images are wanted
-(``inerf_frame_to_u8``), a quarter of the bytes.  The ray batch of a pose comes from ``inerf_gen_rays``.
+(``inerf_frame_to_u8``), a quarter of the bytes.  The ray batch of a pose comes from ``inerf_gen_rays`` (``inerf_gen_rays_ndc`` for NDC frames).
 """
 import os
 import struct

@@ -126,10 +126,51 @@ def sample_coarse(rays, t_vals, t_rand=None, lindisp=False, draw=None):
     return z
 
 
-def gen_rays(poses, height, width, fx, fy, cx, cy, near, far, opengl, static_poses=None):
+def _ndc_arg(ndc):
+    """``ndc`` = (sx, sy, near_plane) as an inerf_ndc (each rounded to fp32 once, as ATen rounds a Python scalar), or None."""
+    if ndc is None:
+        return None
+    sx, sy, near_plane = ndc
+    return _capi.Ndc(float(sx), float(sy), float(near_plane))
+
+
+def _rows3(t, name):
+    """``t`` [..., 3] float32 on a HIP device as ([n, 3] view, row stride in floats) without a copy; ValueError when its flattening is
+    no view with inner stride 1 and a row stride of at least 3."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} lives on {t.device}: intrinsicnerf_amd runs only on a HIP device "
+                           "(no CPU / eager fallback exists)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() < 1 or t.shape[-1] != 3:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [..., 3]")
+    try:
+        flat = t.view(-1, 3)
+    except RuntimeError:
+        flat = None
+    if flat is None or flat.stride(1) != 1 or (flat.shape[0] > 1 and flat.stride(0) < 3):
+        raise ValueError(f"{name} (shape {tuple(t.shape)}, strides {tuple(t.stride())}) does not flatten to [n, 3] rows with inner "
+                         "stride 1 and a row stride >= 3 without a copy: pass it .contiguous()")
+    return flat, max(int(flat.stride(0)), 3)
+
+
+def rows3_viewable(t):
+    """Whether ``t`` [..., 3] goes into assemble_rays / ndc_rays as it is (see _rows3)."""
+    try:
+        _rows3(t, "t")
+    except (TypeError, RuntimeError, ValueError):
+        return False
+    return True
+
+
+def gen_rays(poses, height, width, fx, fy, cx, cy, near, far, opengl, static_poses=None, ndc=None):
     """[B * H * W, 11] ray batch ``[o3, d3, near, far, viewdir3]`` of B pinhole cameras through ``inerf_gen_rays``
     (get_rays + render()'s assembly, run_nerf_helpers.py:359-368 + run_nerf.py:99-128 | create_rays, rays.py:223-256).
-    ``poses``: [B, 3, 4] / [B, 4, 4] / [3, 4] / [4, 4] float32 device tensor; bit-identical to the reference's CPU rays."""
+    ``poses``: [B, 3, 4] / [B, 4, 4] / [3, 4] / [4, 4] float32 device tensor; bit-identical to the reference's CPU rays.
+    ``ndc`` = (sx, sy, near_plane): origin and direction go through ndc_rays (run_nerf_helpers.py:381-399, run_nerf.py:117-119) in
+    the same launch (``inerf_gen_rays_ndc``); view directions stay world-space."""
     def prep(t, name):
         t = _dev(t, name)
         if t.dim() == 2:
@@ -144,12 +185,58 @@ def gen_rays(poses, height, width, fx, fy, cx, cy, near, far, opengl, static_pos
         if static_poses.shape != poses.shape:
             raise ValueError("static_poses must have the shape of poses")
     out = _new(poses, b * int(height) * int(width), RAY_FLOATS)
+    coeff = _ndc_arg(ndc)
     with torch.cuda.device(poses.device):
-        rc = _capi.lib().inerf_gen_rays(_ptr(poses), poses.shape[1] * 4, _ptr(static_poses), b, int(height), int(width),
-                                        float(fx), float(fy), float(cx), float(cy), float(near), float(far),
-                                        _capi.CAM_OPENGL if opengl else 0, _ptr(out), _stream(poses))
+        if coeff is None:
+            rc = _capi.lib().inerf_gen_rays(_ptr(poses), poses.shape[1] * 4, _ptr(static_poses), b, int(height), int(width),
+                                            float(fx), float(fy), float(cx), float(cy), float(near), float(far),
+                                            _capi.CAM_OPENGL if opengl else 0, _ptr(out), _stream(poses))
+        else:
+            rc = _capi.lib().inerf_gen_rays_ndc(_ptr(poses), poses.shape[1] * 4, _ptr(static_poses), b, int(height), int(width),
+                                                float(fx), float(fy), float(cx), float(cy), float(near), float(far),
+                                                _capi.CAM_OPENGL if opengl else 0, C.byref(coeff), _ptr(out), _stream(poses))
     _capi.check(rc, "inerf_gen_rays")
     return out
+
+
+def _given_rays(rays_o, rays_d):
+    o, o_stride = _rows3(rays_o, "rays_o")
+    d, d_stride = _rows3(rays_d, "rays_d")
+    if o.shape[0] != d.shape[0] or o.device != d.device:
+        raise ValueError(f"rays_o {tuple(rays_o.shape)} on {rays_o.device} and rays_d {tuple(rays_d.shape)} on {rays_d.device} do not match")
+    return o, o_stride, d, d_stride
+
+
+def assemble_rays(rays_o, rays_d, near, far, ndc=None):
+    """[n, 11] ray batch ``[o3, d3, near, far, viewdir3]`` from GIVEN rays through ``inerf_assemble_rays`` (render(rays=...)'s
+    assembly, run_nerf.py:106-128): view direction = d / |d| with the reference's CPU bits; ``ndc`` = (sx, sy, near_plane) applies
+    ndc_rays to origin and direction.  ``rays_o`` / ``rays_d``: [..., 3] float32 device tensors whose flattening to [n, 3] is a view
+    with inner stride 1 (columns of an [n, 11] batch go in without a copy)."""
+    o, o_stride, d, d_stride = _given_rays(rays_o, rays_d)
+    n = o.shape[0]
+    out = _new(o, n, RAY_FLOATS)
+    coeff = _ndc_arg(ndc)
+    with torch.cuda.device(o.device):
+        rc = _capi.lib().inerf_assemble_rays(_ptr(o), o_stride, _ptr(d), d_stride, n, float(near), float(far),
+                                             None if coeff is None else C.byref(coeff), _ptr(out), _stream(o))
+    _capi.check(rc, "inerf_assemble_rays")
+    return out
+
+
+def ndc_rays(rays_o, rays_d, ndc):
+    """``(o, d)`` of ndc_rays (run_nerf_helpers.py:381-399) in one launch (``inerf_ndc_rays``), each with the leading shape of
+    ``rays_d``; ``ndc`` = (sx, sy, near_plane).  Inputs as in assemble_rays."""
+    if ndc is None:
+        raise ValueError("ndc_rays needs ndc = (sx, sy, near_plane)")
+    o, o_stride, d, d_stride = _given_rays(rays_o, rays_d)
+    n = o.shape[0]
+    o_out, d_out = _new(o, n, 3), _new(o, n, 3)
+    coeff = _ndc_arg(ndc)
+    with torch.cuda.device(o.device):
+        rc = _capi.lib().inerf_ndc_rays(_ptr(o), o_stride, _ptr(d), d_stride, n, C.byref(coeff), _ptr(o_out), _ptr(d_out), _stream(o))
+    _capi.check(rc, "inerf_ndc_rays")
+    shape = tuple(rays_d.shape)
+    return o_out.reshape(shape), d_out.reshape(shape)
 
 
 def frame_to_u8(values):

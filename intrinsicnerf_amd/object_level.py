@@ -557,17 +557,38 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     """Render an image or a ray batch - run_nerf.py:74-139.
 
     Returns ``[rgb_map, disp_map, acc_map, albedo_map, shading_map, residual_map, extras]``.
+
+    With ``use_viewdirs``, the ``[N, 11]`` batch handed to ``batchify_rays`` on a HIP device comes out of ONE launch with the bits
+    the lines below give on the reference's CPU path: a device pose (``ndc`` on or off, static camera allowed) through
+    ``inerf_gen_rays[_ndc]``, given fp32 device rays without autograd with ``ndc=True`` (no static camera) through
+    ``inerf_assemble_rays``.  Everything else - CPU tensors, other dtypes, rays that require grad, given rays with a static
+    camera or with ``ndc=False``, ``use_viewdirs=False`` - is the reference's torch lines.
     """
-    if (c2w is not None and use_viewdirs and not ndc and isinstance(c2w, torch.Tensor) and c2w.is_cuda
+    k_extract = ["rgb_map", "disp_map", "acc_map", "albedo_map", "shading_map", "residual_map"]
+    batch = sh = None
+    if (c2w is not None and use_viewdirs and isinstance(c2w, torch.Tensor) and c2w.is_cuda
             and (c2w_staticcam is None or (isinstance(c2w_staticcam, torch.Tensor) and c2w_staticcam.is_cuda))):
-        # pose -> [H*W, 11] ray batch in one launch (inerf_gen_rays): the same bits as the lines below give on the
-        # reference's CPU path, on every device (torch's own reductions carry no such promise across devices)
-        rays = kernels.gen_rays(c2w.float(), H, W, K[0][0], K[1][1], K[0][2], K[1][2], near, far, True,
-                                None if c2w_staticcam is None else c2w_staticcam.float())
-        all_ret = batchify_rays(rays, chunk, **kwargs)
+        # pose -> [H*W, 11] ray batch in one launch (inerf_gen_rays / inerf_gen_rays_ndc): the same bits as the lines below give
+        # on the reference's CPU path, on every device (torch's own reductions carry no such promise across devices)
+        batch = kernels.gen_rays(c2w.float(), H, W, K[0][0], K[1][1], K[0][2], K[1][2], near, far, True,
+                                 None if c2w_staticcam is None else c2w_staticcam.float(),
+                                 ndc=_ndc_coefficients(H, W, K[0][0], 1.) if ndc else None)
+        sh = (H, W, 3)
+    elif c2w is None and use_viewdirs and ndc and c2w_staticcam is None:
+        rays_o, rays_d = rays
+        if _device_rays(rays_o, rays_d) and not isinstance(near, torch.Tensor) and not isinstance(far, torch.Tensor):
+            # given rays -> [N, 11] in one launch (inerf_assemble_rays): view directions, NDC and the near / far columns with the
+            # reference's CPU bits (run_nerf.py:106-128).  Only with ndc: without it the view directions are what torch's device
+            # norm gives, as before - tests/test_adam_gpu.py::test_three_training_steps_in_place_of_torch_adam compares two
+            # optimisers over three jittered steps and holds its 1e-4 on those bits (0.48 of the bound), not on the CPU's
+            # (4.7 times it); kernels.assemble_rays itself takes ndc=None
+            as_rows = lambda t: t if kernels.rows3_viewable(t) else t.contiguous()
+            batch = kernels.assemble_rays(as_rows(rays_o), as_rows(rays_d), near, far, ndc=_ndc_coefficients(H, W, K[0][0], 1.))
+            sh = rays_d.shape
+    if batch is not None:
+        all_ret = batchify_rays(batch, chunk, **kwargs)
         for k in all_ret:
-            all_ret[k] = torch.reshape(all_ret[k], [H, W] + list(all_ret[k].shape[1:]))
-        k_extract = ["rgb_map", "disp_map", "acc_map", "albedo_map", "shading_map", "residual_map"]
+            all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
         return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, K, c2w)
@@ -718,11 +739,28 @@ def get_rays_np(H, W, K, c2w):
     return np.broadcast_to(c2w[:3, -1], np.shape(rays_d)), rays_d
 
 
+def _ndc_coefficients(H, W, focal, near):
+    """``(sx, sy, near)`` of ndc_rays: the reference's two scalar expressions (run_nerf_helpers.py:387-393) evaluated with the
+    caller's own objects; the kernels round each to fp32 once, as ATen does with a Python scalar."""
+    return -1. / (W / (2. * focal)), -1. / (H / (2. * focal)), near
+
+
+def _device_rays(rays_o, rays_d):
+    """Given rays the one-launch kernels take: two fp32 tensors of one shape [..., 3] on one HIP device, no autograd."""
+    return (isinstance(rays_o, torch.Tensor) and isinstance(rays_d, torch.Tensor) and rays_o.is_cuda and rays_o.device == rays_d.device
+            and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32 and rays_o.shape == rays_d.shape
+            and rays_o.dim() >= 1 and rays_o.shape[-1] == 3 and not rays_o.requires_grad and not rays_d.requires_grad)
+
+
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
-    """Normalised-device-coordinate rays for forward-facing scenes - run_nerf_helpers.py:381-399."""
+    """Normalised-device-coordinate rays for forward-facing scenes - run_nerf_helpers.py:381-399.  Device fp32 tensors without
+    autograd: one HIP launch (inerf_ndc_rays), the reference's CPU bits; CPU tensors: the reference's expressions."""
+    sx, sy, _ = _ndc_coefficients(H, W, focal, near)
+    if _device_rays(rays_o, rays_d) and not isinstance(near, torch.Tensor):
+        as_rows = lambda t: t if kernels.rows3_viewable(t) else t.contiguous()
+        return kernels.ndc_rays(as_rows(rays_o), as_rows(rays_d), (sx, sy, near))
     t = -(near + rays_o[..., 2]) / rays_d[..., 2]
     rays_o = rays_o + t[..., None] * rays_d
-    sx, sy = -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
     o = torch.stack([sx * rays_o[..., 0] / rays_o[..., 2], sy * rays_o[..., 1] / rays_o[..., 2],
                      1. + 2. * near / rays_o[..., 2]], -1)
     d = torch.stack([sx * (rays_d[..., 0] / rays_d[..., 2] - rays_o[..., 0] / rays_o[..., 2]),
