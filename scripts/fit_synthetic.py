@@ -11,10 +11,16 @@ front-end under autograd - the reference's training step (run_nerf.py:868-1027: 
      run from the same initial weights, batches and jitter: a soak of the forward-save / chain / weight-gradient kernels.
 
     python scripts/fit_synthetic.py [--steps 3000] [--torch-steps 1500] [--out gpurun_out/r03_trained_network.txt]
+                                    [--scene {blobs,sharp}] [--net-seed 0] [--checkpoints 3000,10000 --save-weights W.pt]
 
 The scene: five Gaussian density blobs with their own colours inside the chair camera's [2, 6] depth range, white
 background; targets are rendered from the analytic field with 512 midpoint samples per ray (torch, fp64, on the GPU) from
 24 poses of the NeRF-synthetic orbit at 100x100 (the data set itself is not available here).
+
+``--scene sharp`` is a second analytic field behind the same two functions: blobs a quarter as wide and ten times as dense, and one
+thin slab - a target that drives the weights further from their initialisation than the smooth one does (the hold-out networks of
+tests/golden/make_golden_probe_holdout.py).  ``--checkpoints A,B`` saves both networks at those step counts of the one run, next
+to ``--save-weights`` (W.pt -> W.stepA.pt, W.stepB.pt).
 """
 import argparse
 import os
@@ -36,25 +42,37 @@ BLOBS = (  # centre xyz, sigma (width), peak density, colour
     ((0.1, 0.8, 0.5), 0.15, 30.0, (0.90, 0.80, 0.20)),
     ((-0.3, 0.5, -0.7), 0.17, 22.0, (0.70, 0.30, 0.80)),
 )
+SHARP_BLOBS = tuple((c, 0.25 * s, 10.0 * a, rgb) for c, s, a, rgb in BLOBS)      # narrow and high: the same centres and colours
+SHARP_SLABS = (  # centre xyz, unit normal, half-thickness sigma, lateral sigma, peak density, colour
+    ((0.0, 0.0, -0.15), (0.0, 0.0, 1.0), 0.02, 0.6, 150.0, (0.55, 0.55, 0.50)),
+)
+SCENES = {"blobs": (BLOBS, ()), "sharp": (SHARP_BLOBS, SHARP_SLABS)}
 
 
-def analytic_field(pts):
+def analytic_field(pts, scene="blobs"):
     """(density [..], colour [.., 3]) of the synthetic scene at ``pts[.., 3]`` (any float dtype)."""
+    blobs, slabs = SCENES[scene]
     dens, col = 0.0, 0.0
-    for c, s, a, rgb in BLOBS:
+    for c, s, a, rgb in blobs:
         g = a * torch.exp(-((pts - pts.new_tensor(c)) ** 2).sum(-1) / (2.0 * s * s))
+        dens = dens + g
+        col = col + g[..., None] * pts.new_tensor(rgb)
+    for c, nrm, s, lat, a, rgb in slabs:                          # a Gaussian sheet: thin along its normal, wide across it
+        rel = pts - pts.new_tensor(c)
+        h = (rel * pts.new_tensor(nrm)).sum(-1)
+        g = a * torch.exp(-h * h / (2.0 * s * s) - ((rel ** 2).sum(-1) - h * h) / (2.0 * lat * lat))
         dens = dens + g
         col = col + g[..., None] * pts.new_tensor(rgb)
     return dens, col / dens.clamp_min(1e-12)[..., None]
 
 
-def analytic_render(rays, n=512):
+def analytic_render(rays, n=512, scene="blobs"):
     """White-background volume rendering of the analytic field along ``rays[N, 11]`` (fp64, midpoint rule)."""
     r = rays.double()
     o, d, near, far = r[:, 0:3], r[:, 3:6], r[:, 6:7], r[:, 7:8]
     t = (torch.arange(n, device=r.device, dtype=torch.float64) + 0.5) / n
     z = near + (far - near) * t
-    dens, col = analytic_field(o[:, None, :] + d[:, None, :] * z[:, :, None])
+    dens, col = analytic_field(o[:, None, :] + d[:, None, :] * z[:, :, None], scene)
     delta = (far - near) / n * d.norm(dim=-1, keepdim=True)
     alpha = 1.0 - torch.exp(-dens * delta)
     trans = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1.0 - alpha + 1e-10], -1), -1)[:, :-1]
@@ -82,16 +100,17 @@ def make_nets(dev, seed=0):
     return mk(), mk(), ol.NetworkQuery(embed, embed_d)
 
 
-def training_set(dev, n_poses=24, side=100):
+def training_set(dev, n_poses=24, side=100, scene="blobs"):
     rays = torch.cat([camera_rays(360.0 * i / n_poses, side, dev) for i in range(n_poses)], 0)
-    target = torch.cat([analytic_render(rays[i:i + 65536]) for i in range(0, rays.shape[0], 65536)], 0)
+    target = torch.cat([analytic_render(rays[i:i + 65536], scene=scene) for i in range(0, rays.shape[0], 65536)], 0)
     return rays, target
 
 
-def fit(net_c, net_f, query, rays, target, steps, batch=2048, lr=5e-4, seed=1, log_every=0):
+def fit(net_c, net_f, query, rays, target, steps, batch=2048, lr=5e-4, seed=1, log_every=0, at_step=None):
     """``steps`` training steps as run_nerf.py:868-1027 runs them (no_batching=True branch: a random batch of rays,
     perturb = 1, raw_noise_std = 0, white_bkgd, 64+128; loss = img2mse(rgb_map) + img2mse(rgb0); Adam, the reference's
-    exponential lr decay with lrate_decay = 500).  Returns the loss curve."""
+    exponential lr decay with lrate_decay = 500).  ``at_step``: {step count: callable()}, called once that many steps are done.
+    Returns the loss curve."""
     from intrinsicnerf_amd import object_level as ol
     opt = torch.optim.Adam(list(net_c.parameters()) + list(net_f.parameters()), lr=lr, betas=(0.9, 0.999))
     g = torch.Generator(device=rays.device).manual_seed(seed)
@@ -110,6 +129,8 @@ def fit(net_c, net_f, query, rays, target, steps, batch=2048, lr=5e-4, seed=1, l
             for pg in opt.param_groups:                           # run_nerf.py:1021-1026
                 pg["lr"] = lr * (0.1 ** ((it + 1) / (500 * 1000)))
             losses[it] = loss.detach()
+            if at_step and (it + 1) in at_step:
+                at_step[it + 1]()
             if log_every and (it + 1) % log_every == 0:
                 print(f"  step {it + 1}: loss {float(loss):.5f}", flush=True)
             if (it + 1) % 100 == 0 and not bool(torch.isfinite(losses[it - 99:it + 1]).all()):
@@ -205,24 +226,37 @@ def main():
     ap.add_argument("--side", type=int, default=64, help="side of the held-out view")
     ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "r03_trained_network.txt"))
     ap.add_argument("--save-weights", default="")
+    ap.add_argument("--scene", choices=sorted(SCENES), default="blobs", help="the analytic field to fit")
+    ap.add_argument("--net-seed", type=int, default=0, help="seed of the two networks' initialisation")
+    ap.add_argument("--checkpoints", default="", help="A,B,C: also save both networks after that many steps (needs --save-weights)")
     a = ap.parse_args()
+    checkpoints = sorted({int(c) for c in a.checkpoints.split(",") if c})
+    if checkpoints and (not a.save_weights or checkpoints[0] < 1 or checkpoints[-1] > a.steps):
+        ap.error("--checkpoints needs --save-weights and step counts in 1 .. --steps")
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda:0")
     lines = [f"# scripts/fit_synthetic.py --steps {a.steps} --torch-steps {a.torch_steps} --side {a.side} on {torch.cuda.get_device_name(0)}",
              "# analytic 5-blob scene, 24 poses x 100x100 rays, batch 2048, 64+128 samples, perturb 1, Adam 5e-4; object_level.render_rays under autograd"]
-    rays, target = training_set(dev)
-    net_c, net_f, query = make_nets(dev)
+    if a.scene != "blobs" or a.net_seed != 0:
+        lines.append(f"# scene {a.scene}, network seed {a.net_seed}")
+    rays, target = training_set(dev, scene=a.scene)
+    net_c, net_f, query = make_nets(dev, a.net_seed)
+    save = lambda path: torch.save({"coarse": net_c.state_dict(), "fine": net_f.state_dict()}, path)
+    stem, ext = os.path.splitext(a.save_weights)
+    at_step = {c: (lambda c=c: save(f"{stem}.step{c}{ext}")) for c in checkpoints}
+    if a.save_weights:
+        os.makedirs(os.path.dirname(os.path.abspath(a.save_weights)), exist_ok=True)
     t0 = time.perf_counter()
-    losses = fit(net_c, net_f, query, rays, target, a.steps, log_every=max(1, a.steps // 6))
+    losses = fit(net_c, net_f, query, rays, target, a.steps, log_every=max(1, a.steps // 6), at_step=at_step)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     k = max(1, a.steps // 20)
     lines.append(f"## 0. fit: {a.steps} steps in {dt:.1f} s ({dt / a.steps * 1e3:.2f} ms/step); loss (mean of {k} steps) first {losses[:k].mean():.5f} -> last {losses[-k:].mean():.5f}"
                  f"  (train PSNR of the fine map ~ {-10 * np.log10(losses[-k:].mean() / 2):.2f} dB)")
-    summary = evaluate(net_c, net_f, query, dev, a.side, lines)
     if a.save_weights:
-        torch.save({"coarse": net_c.state_dict(), "fine": net_f.state_dict()}, a.save_weights)
+        save(a.save_weights)
+    summary = evaluate(net_c, net_f, query, dev, a.side, lines, target_fn=lambda r: analytic_render(r, scene=a.scene))
     if a.torch_steps > 0:
         lines.append(f"## 4. HIP network backward vs torch layers (INERF_TRAIN_MLP=torch): {a.torch_steps} steps, same initial weights, batches and jitter")
         curves, times = {}, {}

@@ -3,7 +3,12 @@
 The probe culls a point when s < -kappa S on hi-only arithmetic; every other point goes through the exact trunk as an entry of a
 candidate list.  So the raw rows of points with positive (or NaN) density are the ungated kernel's bit for bit, the others carry
 zero colours and a non-positive sigma, and the rendered maps are those of the gate alone and of the ungated path.  Equality is
-``torch.equal`` on the bits."""
+``torch.equal`` on the bits.
+
+kappa was fitted on the bench networks and the lightly trained fixture.  ``test_trained_and_held_out_networks`` runs every trained
+network the project has - that fixture and the two hold-out fits (tests/golden/probe_holdout_*.npz) - through the probe kernel on
+the depths their passes see, and holds the kernel's own (s, S) against the exact kernel's sigma and against the torch restatement
+that the CPU derivation (tests/test_gate_probe_cpu.py) speaks for."""
 import pytest
 import torch
 
@@ -17,7 +22,8 @@ S_C, S_I = 64, 128
 
 @pytest.fixture(autouse=True)
 def _env(monkeypatch):
-    for k in ("INERF_PRECISION", "INERF_F16_KERNEL", "INERF_GATE", "INERF_PROBE", "INERF_GATE_LOG", "INERF_ENC_CACHE", "INERF_GATE_BYTES"):
+    for k in ("INERF_PRECISION", "INERF_F16_KERNEL", "INERF_GATE", "INERF_PROBE", "INERF_PROBE_WG", "INERF_GATE_LOG", "INERF_ENC_CACHE",
+              "INERF_GATE_BYTES"):
         monkeypatch.delenv(k, raising=False)
 
 
@@ -101,6 +107,70 @@ def test_r_of_the_coarse_network():
     r = float(((po[:, 0].double() - plain[:, 3].double()).abs() / po[:, 1].double()).max())
     print(f"coarse network: r = {r:.3e}, 8 r / kappa = {8 * r / gp.KAPPA:.3f}")
     assert 8.0 * r <= gp.KAPPA
+
+
+HELD_OUT_SHAPES = {"coarse": (171, None), "fine_sub_ranges": (37, 4), "fine_ragged": (171, None)}       # (rays, rays per sub-range)
+
+
+def _held_out_case(c, family, shape):
+    """(state dict, rays, depths) of one case: the coarse network on 64 linspace depths, or the fine network on the fine pass's own
+    192 depths (``gp.fine_depths``), on 171 of the family's 256 rays (171 x 192 = 256.5 tiles) or on 37 spread over them."""
+    n_rays, _ = HELD_OUT_SHAPES[shape]
+    rays, z_fine = gp.family_rays(family), gp.fine_depths(family)
+    sel = torch.arange(n_rays) if n_rays == 171 else torch.arange(0, rays.shape[0], rays.shape[0] // n_rays)[:n_rays]
+    rays = rays[sel].contiguous().to(c["dev"])
+    if shape == "coarse":
+        t = torch.linspace(0., 1., S_C, device=c["dev"])
+        return gp.network(family + "_coarse")[0], rays, (rays[:, 6:7] * (1 - t) + rays[:, 7:8] * t).contiguous()
+    return gp.network(family + "_fine")[0], rays, z_fine[sel].contiguous().to(c["dev"])
+
+
+def _held_out_figures(tag, sd, rays, z, plain, po, cand):
+    """Prints and returns (r of the kernel, kernel-to-model distance in S, candidate share)."""
+    s, big_s = po[:, 0].double().cpu(), po[:, 1].double().cpu()
+    with torch.no_grad():
+        s_model, _ = gp.probe_model(sd, gp.positions(rays.cpu(), z.cpu()))
+    r = float(((s - plain[:, 3].double().cpu()).abs() / big_s).max())
+    dist = float(((s - s_model).abs() / big_s).max())
+    share = float(cand.float().mean())
+    print(f"{tag}: {tuple(z.shape)}, sigma > 0 on {float((plain[:, 3] > 0).float().mean()):.4f}, candidates {share:.4f}, r = {r:.3e}, "
+          f"kappa / r = {gp.KAPPA / r:.2f}, kernel vs model {dist:.3e} S")
+    return r, dist, share
+
+
+@pytest.mark.parametrize("shape", list(HELD_OUT_SHAPES))
+@pytest.mark.parametrize("family", gp.HOLDOUT_FAMILIES)
+def test_trained_and_held_out_networks(monkeypatch, family, shape):
+    """37 x 192 in ten sub-ranges of 4 rays (the last of one); 171 x 192: 257 tiles, the last one half full."""
+    c = _setup()
+    sd, rays, z = _held_out_case(c, family, shape)
+    n_rays, rays_per_sub = HELD_OUT_SHAPES[shape]
+    if rays_per_sub is not None:
+        monkeypatch.setenv("INERF_GATE_BYTES", str(rays_per_sub * z.shape[1] * 1028))
+    words = -(-n_rays // 8)
+    status = torch.zeros(words, dtype=torch.int32, device=c["dev"])
+    plain, gated, probed, po = _three_ways(c, _pack(c, sd), rays, z, status=status, status_rays=8)
+    r, dist, share = _held_out_figures(f"{family} {shape}", sd, rays, z, plain, po, ~(po[:, 0] < -gp.KAPPA * po[:, 1]))
+    assert not bool(torch.isnan(po).any()) and int(status.max()) == 0          # every point was probed, none left the f16 range
+    cand = _assert_rows(plain, gated, probed, po)
+    assert r <= gp.KAPPA                                  # the kernel cannot cull a positive density
+    assert dist <= gp.KAPPA / 8                           # ... and stays where the CPU derivation on the model speaks for it
+    assert 0.0 < share < 1.0 and share == float(cand.float().mean())
+
+
+def test_a_held_out_network_in_the_eight_wave_form(monkeypatch):
+    """INERF_PROBE_WG=1 (tests/test_gate_probe_wg2_gpu.py) on a network neither form was tuned or tested on: (s, S) and the raw rows
+    are the default form's bit for bit."""
+    c = _setup()
+    sd, rays, z = _held_out_case(c, "holdout_sharp", "fine_ragged")
+    packed = _pack(c, sd)
+    _, _, probed, po = _three_ways(c, packed, rays, z)
+    monkeypatch.setenv("INERF_PROBE_WG", "1")
+    _, _, probed1, po1 = _three_ways(c, packed, rays, z)
+    print(f"holdout_sharp fine, two forms: candidates {float((~(po[:, 0] < -gp.KAPPA * po[:, 1])).float().mean()):.4f}")
+    assert not bool(torch.isnan(po).any())
+    assert torch.equal(_bits(po), _bits(po1))
+    assert torch.equal(_bits(probed), _bits(probed1))
 
 
 def _with_alpha_bias(sd, shift):
