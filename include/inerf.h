@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40017
+#define INERF_ABI_VERSION 40018
 
 /* error codes */
 #define INERF_OK              0
@@ -937,6 +937,49 @@ typedef struct inerf_batch_args {
     int32_t* status;
 } inerf_batch_args;
 int inerf_batch_assemble(const inerf_batch_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh extraction: the query lattice of a scene's oriented bounding box and the occupancy of a trained network on it
+ * (SSR/extract_colour_mesh.py:149-185, SSR/geometry/occupancy.py:5-48).  Marching cubes stays with the caller (skimage, on the
+ * returned array); the vertex-colour rays are ordinary inerf_render_rays launches.
+ * ------------------------------------------------------------------------------------------- */
+#define INERF_MAX_GRID_DIM 1024           /* points per lattice axis: dim^3 <= 2^30 fits the kernels' 32-bit point index */
+
+/* Lattice points [first, first + count) of make_3D_grid (occupancy.py:24-48) as rows of three floats.  Lattice index
+ * g = (i * dim + j) * dim + k (torch.meshgrid 'ij': the last axis fastest) lies at
+ *   gx = t[i] * scale[0], gy = t[j] * scale[1], gz = t[k] * scale[2]                                        (occupancy.py:34)
+ *   out[r] = ((M[r][0] * gx + M[r][1] * gy) + M[r][2] * gz) + M[r][3],  r = 0..2                         (occupancy.py:36-46)
+ * every product and every sum rounded to fp32 on its own, in this order: the bits of the reference's CPU tensors
+ * (tests/golden/grid_query.npz).  t: [dim] device floats, the axis table - torch.linspace(occ_range[0], occ_range[1], dim)
+ * (occupancy.py:25), evaluated by the caller, whose roundings no closed form reproduces (as t_vals of inerf_sample_coarse);
+ * scale[3] [host]: extents / (0.9 (occ_range[1] - occ_range[0])) rounded to fp32 (occupancy.py:6-11); transform[12] [host]:
+ * rows 0..2 of the box-to-scene matrix, row-major 3 x 4, rounded to fp32 (occupancy.py:9).  Both host arrays travel by value in the
+ * kernel arguments.  2 <= dim <= INERF_MAX_GRID_DIM, 0 <= first, first + count <= dim^3, else INERF_E_INVALID; count == 0 is fine. */
+int inerf_grid_points(const float* t, int dim, const float* scale /*[host] 3*/, const float* transform /*[host] 12*/,
+                      int64_t first, int64_t count, float* out /*[count,3]*/, void* stream);
+
+/* The same function of the same arguments on HOST pointers (t and out included), evaluated by the calling thread: the operation
+ * order above can be pinned, and CPU tensors served (geometry.make_3D_grid), without a device. */
+int inerf_grid_points_host(const float* t /*[host]*/, int dim, const float* scale /*[host] 3*/, const float* transform /*[host] 12*/,
+                           int64_t first, int64_t count, float* out /*[host] [count,3]*/);
+
+/* Occupancy of lattice points [first_point, first_point + n_points) in ONE launch: replaces the chunk loop over run_network, the
+ * `.cpu()` after every 1 024 points, raw[..., 3] and occupancy_activation (extract_colour_mesh.py:156-164, 172-179):
+ *   sigma = alpha_linear(trunk(embed(x / xyz_div)))  with x = the lattice point as inerf_grid_points gives it
+ *   occ_out[i] = 1 - exp(-relu(sigma) * dist)  (a NaN sigma gives NaN, as F.relu does);  sigma_out[i] = sigma  (sigma_out may be NULL)
+ * for i = 0 .. n_points - 1.  The density depends on the position alone, so only the position encoding and the eight trunk layers
+ * run - neither the direction encoding nor a colour, feature, view or semantic layer - and 4 (8 with sigma_out) bytes per point
+ * leave the kernel.  sigma has the bits of channel 3 of inerf_encode_mlp on rays (o = x, d = 0, z = 0): it is the same device code.
+ * INERF_PREC_F16X3 only (INERF_E_UNSUPPORTED otherwise; callers evaluate inerf_grid_points through inerf_encode_mlp then), both
+ * variants, any class count (the semantic head is not evaluated), l_xyz / l_dir as inerf_encode_mlp.  dim, first_point and
+ * n_points as inerf_grid_points.  status: NULL or INERF_STATUS_* words as in inerf_encode_mlp_chunked, here one word per
+ * `status_points` LATTICE points - a tile that leaves the f16 range sets word (lattice index / status_points) of every point it
+ * holds, so the words cover the whole lattice ([ceil(dim^3 / status_points)]) whatever sub-range a launch takes; status_points == 0:
+ * one word.  Null or out-of-range arguments return before anything touches the device. */
+int inerf_occupancy_grid(const inerf_net_desc* net, const float* packed_weights, const float* t, int dim,
+                         const float* scale /*[host] 3*/, const float* transform /*[host] 12*/, float dist, int64_t first_point,
+                         int64_t n_points, float* occ_out /*[n_points]*/, float* sigma_out /*[n_points] or NULL*/,
+                         int32_t* status, int64_t status_points, void* stream);
 
 #ifdef __cplusplus
 }

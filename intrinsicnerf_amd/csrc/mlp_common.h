@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "grid.h"
 #include "layout.h"
 
 namespace inerf {
@@ -37,6 +38,11 @@ struct MlpParams {
     int* cand_idx;                  // point index within the sub-range per candidate, in reservation order
     unsigned int* cand_count;       // the sub-range's candidate count (zeroed by the launcher)
     float* probe_out;               // tests only, optional: [n_points, 2] = (s, S) of the probe per point
+    // occupancy grid (mlp_f16_t128.hip kGridTrunk; appended likewise): point gp of the launch is lattice index ray0 + gp of `grid`
+    GridSpec grid;
+    float grid_dist;                // occ = 1 - exp(-relu(sigma) * grid_dist)
+    float* occ;                     // [n_points]
+    float* sigma_out;               // [n_points] or nullptr
 };
 
 struct GatePlan {
@@ -89,6 +95,7 @@ int record(hipError_t e);
 int launch_mlp_f32(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream);
 int launch_mlp_f16x3(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream);   // p.save != nullptr: saving variant
 int launch_mlp_f16x3_t128(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream);      // inference on the 128-point tile (mlp_f16_t128.hip)
+int launch_grid_trunk_f16x3(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream);    // ... its occupancy-grid mode: position, trunk, sigma
 bool mlp_f16x3_takes_t128(bool ssr, bool save, bool endpoint, int n_classes);                   // which launches take it
 int64_t enc_cache_bytes_t128(int64_t n_points);                                                 // object-level inference on the 128-point tile: the parked encoding
 int64_t sem_scratch_bytes_t128(int64_t n_points);                                               // ... and the SSR form's scratch (classes > 0)

@@ -10,17 +10,25 @@ namespace inerf {
 // point r left the f16 range
 __device__ __forceinline__ int* pad_words(_Float16* ldst, int r) { return reinterpret_cast<int*>(ldst + r * kRowD + kWidth + kDirCols); }
 
-// Position encoding of point gp (ray r) into columns 0..63 of `row`: x = o + d z, thread `part` of the point's kParts takes every kParts-th
-// frequency, part kXyzPart the raw xyz and the zero fill.  Store: split_store (hi | lo), hi_store_parked (hi | the same in the lo plane) or
-// hi_store (the hi plane alone: kLoPlane = 0, nothing behind the hi plane is zeroed either).
-template <bool kSsr, int kParts, int kXyzPart, auto Store, int kLoPlane>
+// Position encoding of point gp into columns 0..63 of `row`: x = o + d z of ray r, or (kGrid, the occupancy grid: r unused) lattice point
+// ray0 + gp of p.grid (grid.h); thread `part` of the point's kParts takes every kParts-th frequency, part kXyzPart the raw xyz and the zero
+// fill.  Store: split_store (hi | lo), hi_store_parked (hi | the same in the lo plane) or hi_store (the hi plane alone: kLoPlane = 0, nothing
+// behind the hi plane is zeroed either).
+template <bool kSsr, int kParts, int kXyzPart, auto Store, int kLoPlane, bool kGrid = false>
 __device__ __forceinline__ void encode_position(const MlpParams& p, const float* __restrict__ r, int gp, int part, _Float16* row, float& amax) {
-    const float zz = __builtin_nontemporal_load(p.z + gp);
     float x[3];
+    if constexpr (kGrid) {
+        grid_point(p.grid, p.ray0 + gp, x);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));                                // run_nerf.py:488
-        if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);              // semantic_nerf.py:64
+        for (int c = 0; c < 3; ++c)
+            if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);          // semantic_nerf.py:64
+    } else {
+        const float zz = __builtin_nontemporal_load(p.z + gp);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            x[c] = __fadd_rn(r[c], __fmul_rn(r[3 + c], zz));                            // run_nerf.py:488
+            if (kSsr && p.xyz_div != 1.0f) x[c] = __fdiv_rn(x[c], p.xyz_div);          // semantic_nerf.py:64
+        }
     }
     for (int f = part; f < p.l_xyz; f += kParts) {
         const float s = (float)(1 << f);

@@ -99,7 +99,10 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 //   kGateTrunk with kListed: persistent over ceil(*cand_count / 128) tiles of the candidate list - a row's point comes from the list, its
 //               exact sigma is scattered into that point's raw row, its record carries the original index (the heads kernel is the same).
 //               A point's column of every GEMM depends on that point alone: the same bits as the unlisted trunk's.
-enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3 };
+//   kGridTrunk  (occupancy grid of mesh extraction, both networks: inerf_occupancy_grid) kGateTrunk up to and including sigma on the points of
+//               a lattice: point gp is lattice index ray0 + gp (grid_point(), grid.h; SSR: / xyz_div), and all that leaves is
+//               occ[gp] = 1 - exp(-relu(sigma) grid_dist) and, when asked for, sigma_out[gp] - no raw rows, no records, no atomics.
+enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3, kGridTrunk = 4 };
 constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
 // The probe's margin: the smallest power of two >= 8 x the largest |s - sigma| / S measured on the GPU (profiles/gate_probe_margin.txt).
 constexpr float kProbeKappa = 0x1p-6f;
@@ -112,7 +115,8 @@ template <bool kSsr, bool kSave, bool kPipe, int kMode, bool kListed = false>
 __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     static_assert(!(kSsr && kSave), "the saving form is the object-level network's");
     static_assert(!kPipe || (!kSsr && !kSave), "the pipelined trunk is the object-level inference form");
-    static_assert(kMode == kWhole || (!kSsr && !kSave && !kPipe), "the density gate is the object-level inference form's");
+    static_assert(kMode == kWhole || kMode == kGridTrunk || (!kSsr && !kSave && !kPipe), "the density gate is the object-level inference form's");
+    static_assert(kMode != kGridTrunk || (!kSave && !kPipe), "the occupancy grid is an inference form");
     static_assert(!kListed || kMode == kGateTrunk, "the candidate list feeds the gated trunk");
     constexpr int kParts = 512 / kPtsT;
     // the wide GEMMs' first products take a zero C operand instead of 64 v_mov in front of every GEMM (wide_gemm_h PEEL): +1.3 % same-box,
@@ -182,9 +186,9 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             const float* __restrict__ r = p.rays + (size_t)ray * INERF_RAY_FLOATS;
             _Float16* row = ldst + pt * kRowD;
             constexpr auto kStore = kMode == kGateProbe ? &hi_store_parked<kPlaneT> : &split_store<kPlaneT>;
-            if constexpr (kMode != kGateHeads)        // (the gated heads' rows arrive with h7 in these columns)
-                encode_position<kSsr, kParts, 2, kStore, kPlaneT>(p, r, gp, part, row, amax);
-            if constexpr (kMode != kGateTrunk && kMode != kGateProbe) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
+            if constexpr (kMode != kGateHeads)        // (the gated heads' rows arrive with h7 in these columns; the grid's point is a lattice point)
+                encode_position<kSsr, kParts, 2, kStore, kPlaneT, kMode == kGridTrunk>(p, r, gp, part, row, amax);
+            if constexpr (kMode != kGateTrunk && kMode != kGateProbe && kMode != kGridTrunk) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
                 const int fd = kParts - 1 - part;
                 if (fd < p.l_dir) {
                     const float s = (float)(1 << fd);
@@ -224,7 +228,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
 #ifdef INERF_ABL_NO_ENCODE      // (timing ablation of a development build: the first tile's encoding stays in LDS; results are wrong)
         if (tile == (int)blockIdx.x)
 #endif
-        encode(kMode != kGateTrunk && kMode != kGateProbe);
+        encode(kMode != kGateTrunk && kMode != kGateProbe && kMode != kGridTrunk);
         __syncthreads();
         // park the encoding for the skip layer (piece q = tid + 512 i of the tile's 2 048 sixteen-byte pieces: plane q / 1024, row (q % 1024) / 8)
         const bool enc_cached = !kSsr && !kSave && kMode == kWhole && p.sem_scratch != nullptr;
@@ -243,7 +247,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             }
         }
         // gated trunk: the same pieces parked in LDS (park_encoding, mlp_f16_gate.h)
-        constexpr bool kPark = kMode == kGateTrunk && INERF_GATE_TRUNK_PARK;
+        constexpr bool kPark = (kMode == kGateTrunk || kMode == kGridTrunk) && INERF_GATE_TRUNK_PARK;
         if constexpr (kPark) park_encoding<2, 512>(ldst, tid, false);
         auto encode_again = [&]() {         // the encoding back into columns 0..63 (sc0: past the vector L1, whose lines of an earlier tile may be stale)
             if constexpr (kPark) {
@@ -408,7 +412,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[6], 16), xr, 0, 0, lane_t, am1);
             store256(L.trunk[6], true, SAVE_H0 + 6, pf32(L.trunk[7], 16), kWithBits);
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[7], 16), xr, 0, 0, lane_t, am1);
-            if constexpr (kMode == kGateTrunk) store256(L.trunk[7], true, SAVE_H7, pf32(L.trunk[0], 4), kWithBits);
+            if constexpr (kMode == kGateTrunk || kMode == kGridTrunk) store256(L.trunk[7], true, SAVE_H7, pf32(L.trunk[0], 4), kWithBits);
             else                               store256(L.trunk[7], true, SAVE_H7, pf256(L.as1, 16), kWithBits);
         }
 
@@ -450,6 +454,22 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             // trunk cannot overflow on a point the probe did not flag.  A listed tile holds points of rays from anywhere in the sub-range:
             // a per-tile flag here would mark the words of rays whose own points are in range (and have their chunks rendered again).
             if constexpr (!kListed) flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
+            __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
+            continue;
+        }
+
+        // ---------------- occupancy grid: sigma as above, then the activation of extract_colour_mesh.py:172-175 ----------------
+        if constexpr (kMode == kGridTrunk) {
+            const int pt16 = tile * kPtsT + 16 * wave;
+            const _Float16* const xs_g = ldst + (16 * wave + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
+            const float sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];      // lanes 0..15: this wave's points
+            if (lane_t < 16 && pt16 + lane_t < p.n_points) {
+                float occ = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(sigma, 0.0f), p.grid_dist)));      // as the compositing kernel's alpha (ray_ops.hip)
+                if (sigma != sigma) occ = sigma;                                                      // relu(NaN) stays NaN in torch
+                __builtin_nontemporal_store(occ, p.occ + pt16 + lane_t);
+                if (p.sigma_out) __builtin_nontemporal_store(sigma, p.sigma_out + pt16 + lane_t);
+            }
+            flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
             __syncthreads();                       // the rows are read: the next tile's encode may overwrite them
             continue;
         }
@@ -704,6 +724,8 @@ __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_f16x3(const MlpParams
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_heads_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateHeads>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_probe_f16(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateProbe>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_listed_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk, true>(p); }
+template <bool kSsr>
+__global__ __launch_bounds__(512, 2) void k_grid_trunk_f16x3(const MlpParams p) { encode_mlp_t128_tiles<kSsr, false, false, kGridTrunk>(p); }
 
 }  // namespace inerf
 #include "mlp_f16_probe.h"      // k_mlp_gate_probe_wg2_f16: the probe as two four-wave workgroups per CU
@@ -812,6 +834,21 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         fprintf(stderr, "\n");
     }
     return record(e);
+}
+
+// The occupancy grid's launch: like the gated trunk's - one eight-wave workgroup per CU with the parked encoding's extension area, persistent over the tiles.
+int launch_grid_trunk_f16x3(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream) {
+    p.n_tiles = (int)((n_points + kPtsT - 1) / kPtsT);
+    const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
+    void (*kern)(const MlpParams) = ssr ? k_grid_trunk_f16x3<true> : k_grid_trunk_f16x3<false>;
+    static PerDeviceOnce attr_sets[2];
+    if (attr_sets[ssr].first()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesTrunk);
+        if (e != hipSuccess) return record(e);
+        attr_sets[ssr].mark();
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);
+    return record(hipGetLastError());
 }
 
 int launch_mlp_f16x3_t128(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream) {

@@ -239,6 +239,55 @@ def ndc_rays(rays_o, rays_d, ndc):
     return o_out.reshape(shape), d_out.reshape(shape)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# mesh extraction (include/inerf.h, "Mesh extraction"): the query lattice and the occupancy of a network on it
+# ---------------------------------------------------------------------------------------------------------------------
+def _grid_arg(t, scale, transform):
+    """(t as a contiguous fp32 vector, dim, float[3], float[12]) of the lattice entry points; ``scale`` (3 numbers) and ``transform`` (the
+    3 x 4 rows of the box-to-scene matrix, 12 numbers) are rounded to fp32 here, once, like ``Tensor.float()``."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1:
+        raise ValueError("t must be a float32 vector (torch.linspace(occ_range[0], occ_range[1], dim))")
+    scale, transform = [float(v) for v in scale], [float(v) for v in transform]
+    if len(scale) != 3 or len(transform) != 12:
+        raise ValueError(f"scale holds {len(scale)} numbers and transform {len(transform)}, expected 3 and 12 (rows 0..2 of the 3 x 4 matrix)")
+    return t.contiguous(), int(t.shape[0]), (C.c_float * 3)(*scale), (C.c_float * 12)(*transform)
+
+
+def grid_points(t, scale, transform, first=0, count=None):
+    """Lattice points ``[first, first + count)`` of make_3D_grid (SSR/geometry/occupancy.py:24-48) as a ``[count, 3]`` tensor where ``t``
+    lives: ``inerf_grid_points`` for a device table, ``inerf_grid_points_host`` for a CPU one - the same bits either way."""
+    t, dim, sc, m = _grid_arg(t, scale, transform)
+    count = dim ** 3 - int(first) if count is None else int(count)
+    out = torch.empty(max(count, 0), 3, dtype=torch.float32, device=t.device)
+    if t.is_cuda:
+        with torch.cuda.device(t.device):
+            rc = _capi.lib().inerf_grid_points(_ptr(t), dim, sc, m, int(first), count, _ptr(out), _stream(t))
+        _capi.check(rc, "inerf_grid_points")
+    else:
+        _capi.check(_capi.lib().inerf_grid_points_host(_ptr(t), dim, sc, m, int(first), count, _ptr(out)), "inerf_grid_points_host")
+    return out
+
+
+def occupancy_grid(desc, packed, t, scale, transform, dist, first=0, count=None, occ=None, sigma=None, status=None, status_points=0):
+    """``occ[count] = 1 - exp(-relu(sigma) * dist)`` of lattice points ``[first, first + count)`` in one ``inerf_occupancy_grid`` launch
+    (position encoding, trunk and density head only).  ``occ`` / ``sigma``: optional float32 device vectors of ``count`` elements to write
+    into (``sigma=True``: allocate one; None: sigma is not stored).  ``status``: int32 device words, one per ``status_points`` LATTICE points
+    (word = lattice index // status_points; 0: one word).  Returns ``(occ, sigma or None)``."""
+    t, dim, sc, m = _grid_arg(_dev(t, "t"), scale, transform)
+    packed = _dev(packed, "packed weights", (None,))
+    count = dim ** 3 - int(first) if count is None else int(count)
+    occ = _new(t, max(count, 0)) if occ is None else occ
+    sigma = _new(t, max(count, 0)) if sigma is True else sigma
+    for name, o in (("occ", occ), ("sigma", sigma)):
+        if o is not None and (not o.is_cuda or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != max(count, 0) or o.device != t.device):
+            raise ValueError(f"{name} must be a contiguous float32 vector of {count} elements on {t.device}")
+    with torch.cuda.device(t.device):
+        rc = _capi.lib().inerf_occupancy_grid(desc, _ptr(packed), _ptr(t), dim, sc, m, float(dist), int(first), count, _ptr(occ), _ptr(sigma),
+                                              None if status is None else C.c_void_p(status.data_ptr()), int(status_points), _stream(t))
+    _capi.check(rc, "inerf_occupancy_grid")
+    return occ, sigma
+
+
 def frame_to_u8(values):
     """``(255 * clip(x, 0, 1)).astype(uint8)`` (to8b, run_nerf_helpers.py:13) on the device; same shape, dtype uint8."""
     values = _dev(values, "values")

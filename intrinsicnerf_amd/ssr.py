@@ -459,6 +459,15 @@ class SSRRenderMixin:
         return (st("rgb"), st("disp"), st("dep"), st("vis_dep"), st("sem"), st("vis_sem"), st("ent"), st("vis_ent"),
                 st("albedo"), st("shading"), st("residual"), cluster_manager)
 
+    def occupancy_grid(self, extents, transform, grid_dim=256, occ_range=(-1., 1.)):
+        """``occ[grid_dim, grid_dim, grid_dim]`` (device) of the fine network on the lattice inside the scene's oriented bounding box -
+        extract_colour_mesh.py:149-185 up to the array handed to marching cubes: ``extents`` / ``transform`` as
+        trimesh.bounds.oriented_bounds gives them (transform = the inverse of its to-origin matrix), voxel size
+        ``(far - near) / N_importance`` (:178).  One ``inerf_occupancy_grid`` launch (geometry.occupancy_grid)."""
+        from . import geometry
+        return geometry.occupancy_grid(self.ssr_net_fine, self.embed_fn, occ_range, extents, transform, grid_dim,
+                                       (self.far - self.near) / self.N_importance, embeddirs_fn=self.embeddirs_fn)
+
     def _coalesced(self, flat_rays):
         """``self.chunk``, or the larger number of rays per ``volumetric_rendering`` call that gives the same frame
         (kernels.coalesced_chunk; results are bit-identical for any chunking): only when no random number is drawn per chunk (eval
