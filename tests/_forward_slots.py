@@ -226,14 +226,17 @@ def fused_positions(rays, z):
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernel and its buffer
 # ---------------------------------------------------------------------------------------------------------------------
-def run_train_forward(desc, packed, rays, z, endpoint=False):
+def run_train_forward(desc, packed, rays, z, endpoint=False, raw=None):
     """inerf_encode_mlp_train through the C ABI on a sentinel-filled buffer: (raw [n, s, ch], the buffer as int32 words,
-    act_max as a float, status as an int), synchronised."""
+    act_max as a float, status as an int), synchronised.  ``raw``: a caller-owned contiguous fp32 view of n * s * ch floats to write
+    the rows into (returned as it is) instead of a fresh tensor."""
     lib = _capi.lib()
     dev = rays.device
     n, s = z.shape
     flags = kernels.FLAG_ENDPOINT if endpoint else 0
-    raw = torch.zeros(n, s, lib.inerf_raw_channels(desc, flags, 1), device=dev)
+    if raw is None:
+        raw = torch.zeros(n, s, lib.inerf_raw_channels(desc, flags, 1), device=dev)
+    assert raw.is_contiguous() and raw.dtype == torch.float32 and raw.numel() == n * s * lib.inerf_raw_channels(desc, flags, 1)
     save = torch.full((lib.inerf_mlp_save_floats(desc, n * s),), SENTINEL, dtype=torch.int32, device=dev)
     act_max = torch.zeros(1, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -1,0 +1,237 @@
+"""The raw rows of the fused forward kernels - [rgb, sigma, albedo, shading, residual | logits | endpoint] per sample point -
+against fp64 at the yardstick of the forward-slots tests: per channel group  max |got - fp64| <= 4 D + 2^-21 max |fp64|,
+D = how far the reference's own fp32 forward lands from fp64 on the same points (tests/_forward_slots.py has the reference).
+
+``weights``: the default-init network of the slot tests (``plain``) or the same with gains on the OUTPUT layers (``sharp``:
+density 512, the three sigmoid heads 32, the logits 64 - weights only) so that sigma has both signs, the sigmoids leave their
+linear middle and the logits have both signs; ``case_weights`` then moves alpha_linear.bias by minus the fp64 median of sigma
+over the case's points and centres the residual head (_centre_sharp).  ``reference`` is computed once per case and shared by every form.  ``judge`` prints one line per
+group and appends what is over; ``RawBuffer`` / ``launch`` run inerf_encode_mlp_probed into a caller-owned, sentinel-filled,
+guarded view (optionally one float off a sixteen-byte boundary)."""
+import ctypes as C
+import functools
+
+import torch
+import torch.nn.functional as F
+
+import _forward_slots as fs
+import oracle
+from intrinsicnerf_amd import _capi, kernels
+
+TAG = "raw_rows |"               # every figure printed from here starts with it
+WEIGHT_SEED = 11                 # the slot tests' network
+# 4 = 2^(24 - 22): the kernels' operands (f16 hi + lo) carry 22 bits where the fp32 reference's carry 24 (test_forward_slots_gpu.py)
+YARDSTICK_FACTOR = 4.0
+GROUP_FACTORS = {}               # a group whose factor had to be raised (none: the docstring of test_raw_rows_gpu.py has the figures)
+REL_TERM = 2.0 ** -21
+GUARD = 16                       # sentinel words either side of the rows
+SHARP_GAINS = {"sigma": 512.0, "albedo": 32.0, "shading": 32.0, "residual": 32.0, "logits": 64.0}   # per group: on its output layer
+KEEP_SLOTS_UP_TO = 1024          # points up to which a case keeps the last slots (the CPU module continues from them)
+LAST_SLOTS = (kernels.SAVE_H0 + 7, kernels.SAVE_AS1H, kernels.SAVE_VH, kernels.SAVE_SEMH)
+
+
+def groups(variant, classes, endpoint):
+    """{name: (first, end)} of a raw row's channel groups, in row order."""
+    g = {"rgb": (0, 3), "sigma": (3, 4), "albedo": (4, 7), "shading": (7, 8), "residual": (8, 11)}
+    c = 11
+    if classes:
+        g["logits"] = (c, c + classes)
+        c += classes
+    if endpoint and variant == "ssr":
+        g["endpoint"] = (c, c + 128)
+    return g
+
+
+def output_layers(variant, classes):
+    """{the group an output layer writes: its name in the state dict} (object_level.NeRF calls its shading head test_linear and its
+    residual head shading_linear)."""
+    ssr = variant == "ssr"
+    layers = {"sigma": "alpha_linear", "albedo": "albedo_linear2", "shading": "shading_linear2" if ssr else "test_linear2",
+              "residual": "residual_linear" if ssr else "shading_linear"}
+    if classes:
+        layers["logits"] = "semantic_linear.1"
+    return layers
+
+
+def split(p):
+    """(rays, samples per ray) with rays * samples = p: the largest sample count up to 24 that divides p (the slot tests' split)."""
+    s = max(k for k in range(1, 25) if p % k == 0)
+    return p // s, s
+
+
+def weights(variant, classes, kind):
+    """A fresh state dict: ``plain`` - oracle.make_state_dict(seed 11); ``sharp`` - the same with the output layers' WEIGHTS (biases
+    untouched) times SHARP_GAINS.  (``case_weights`` adds the per-case shift of alpha_linear.bias.)"""
+    sd = oracle.make_state_dict(variant, classes, seed=WEIGHT_SEED)
+    if kind == "sharp":
+        for group, layer in output_layers(variant, classes).items():
+            sd[layer + ".weight"] = sd[layer + ".weight"] * SHARP_GAINS[group]
+    elif kind != "plain":
+        raise ValueError(kind)
+    return sd
+
+
+def _split_point(values):
+    """A value no element of ``values`` [p] sits on, with half of them either side: the midpoint of the two middle order statistics (an odd
+    count: of the middle one and its lower neighbour)."""
+    v = values.sort()[0]
+    k = v.numel() // 2
+    return float((v[k - 1] + v[k]) / 2)
+
+
+def _centre_sharp(variant, classes, sd, slots64):
+    """The per-case part of ``sharp``, on the case's own fp64 slots.  alpha_linear.bias moves by minus the median of sigma (_split_point: no
+    point is left at zero), so that either sign has half of the points.  The residual head's three biases move by minus their channel's
+    median pre-activation, and its gain is doubled from SHARP_GAINS' 32 until some output of the group is below 0.045 and some above 0.91:
+    at 65 points the uncentred head at 32 stays inside [0.22, 0.78] (C = 32: [0.46, 0.96]) - test_raw_rows_cpu.py asks for 0.05 and 0.9."""
+    layers = output_layers(variant, classes)
+    h7, vh = slots64[kernels.SAVE_H0 + 7], slots64[kernels.SAVE_VH]
+    w, b = sd["alpha_linear.weight"].double(), sd["alpha_linear.bias"].double()
+    sd["alpha_linear.bias"] = (b - _split_point(F.linear(h7, w, b)[:, 0])).float()
+    res = layers["residual"]
+    base, b = sd[res + ".weight"], sd[res + ".bias"].double()
+    for doublings in range(6):
+        w = base * 2.0 ** doublings
+        pre = F.linear(vh, w.double(), b)
+        shifted = (b - torch.stack([torch.tensor(_split_point(pre[:, c])) for c in range(3)]).double()).float()
+        out = torch.sigmoid(F.linear(vh, w.double(), shifted.double()))
+        if doublings == 0:
+            sd[res + ".weight"], sd[res + ".bias"] = w, shifted      # (a case of a few points may reach neither: it keeps the gain of 32)
+        if float(out.min()) < 0.045 and float(out.max()) > 0.91:
+            sd[res + ".weight"], sd[res + ".bias"] = w, shifted
+            return
+
+
+@functools.lru_cache(maxsize=None)
+def _case(variant, classes, endpoint, p, kind):
+    ssr = variant == "ssr"
+    n, s = split(p)
+    rays, z = fs.rays_and_depths(n, s, seed=p % 1000, origin_scale=3.0 if ssr else 1.0)
+    div = 10.0 if ssr else 1.0
+    sd = weights(variant, classes, kind)
+    slots64 = fs.reference_slots(fs.make_module(variant, classes, sd), rays, z, div, endpoint)
+    if kind == "sharp" and p >= 2:     # (one point has no median to split at: it keeps the gains alone, and sigma its natural magnitude)
+        _centre_sharp(variant, classes, sd, slots64)
+        # the output layers alone have changed: the rows are the heads on the same last slots (test_forward_slots_cpu.py: bit for bit the module's)
+        slots64["raw"] = fs.heads_from_slots(fs.make_module(variant, classes, sd), slots64, endpoint)
+    slots32 = fs.reference_slots(fs.make_module(variant, classes, sd), rays, z, div, endpoint, dtype=torch.float32)
+    keep = ("raw",) + (LAST_SLOTS if p <= KEEP_SLOTS_UP_TO else ())
+    return {"sd": sd, "rays": rays, "z": z, "slots64": {k: slots64[k] for k in keep}, "raw32": slots32["raw"]}
+
+
+def case_weights(variant, classes, endpoint, p, kind):
+    """The state dict of one case (a copy): ``weights`` and, ``sharp``, the per-case centring of _centre_sharp."""
+    return {k: t.clone() for k, t in _case(variant, classes, endpoint, p, kind)["sd"].items()}
+
+
+def reference(variant, classes, endpoint, p, kind):
+    """(rays, z, raw64, raw32) of one case on the CPU - computed once, shared by the forms, left alone."""
+    c = _case(variant, classes, endpoint, p, kind)
+    return c["rays"], c["z"], c["slots64"]["raw"], c["raw32"]
+
+
+def last_slots(variant, classes, endpoint, p, kind):
+    """{slot: fp64 value} of h7, as1h, vh, semh (and "raw") of a case of at most KEEP_SLOTS_UP_TO points."""
+    return _case(variant, classes, endpoint, p, kind)["slots64"]
+
+
+def module(variant, classes, endpoint, p, kind):
+    return fs.make_module(variant, classes, case_weights(variant, classes, endpoint, p, kind))
+
+
+def bound_of(raw64, raw32, name, span):
+    """(bound, D) of one channel group: 4 D + 2^-21 max |fp64| over the group (GROUP_FACTORS: a raised factor, with its reason)."""
+    want = raw64[:, span[0]:span[1]]
+    d = float((raw32[:, span[0]:span[1]].double() - want).abs().max()) if want.numel() else 0.0
+    return GROUP_FACTORS.get(name, YARDSTICK_FACTOR) * d + REL_TERM * (float(want.abs().max()) if want.numel() else 0.0), d
+
+
+def _rows_and_tiles(mask):
+    rows = mask.any(1).nonzero().flatten()
+    return rows, sorted(set((rows // 64).tolist()))
+
+
+def judge(got, raw64, raw32, groups, tag, problems, rows=None, only=None):
+    """Per channel group of ``groups``: print  err, D, err / D, err / bound, range  and append to ``problems`` how many values are over
+    the bound, in how many points and which 64-point tiles - or how many words still hold the sentinel.  ``got``: fp32 [p, ch] as the
+    kernel left it.  ``rows`` (bool [p]): judge these points only (D and the range stay those of the whole group); ``only``: these
+    groups only.  Returns {group: (err, D, bound)}."""
+    got = got.detach().cpu()
+    p = got.shape[0]
+    assert got.dtype == torch.float32 and tuple(got.shape) == tuple(raw64.shape) == tuple(raw32.shape), (got.shape, raw64.shape, raw32.shape)
+    sel = torch.ones(p, dtype=torch.bool) if rows is None else rows
+    unwritten = got.contiguous().view(torch.int32) == fs.SENTINEL
+    out = {}
+    for name, (a, b) in groups.items():
+        if only is not None and name not in only:
+            continue
+        want = raw64[:, a:b]
+        bound, d = bound_of(raw64, raw32, name, (a, b))
+        left = unwritten[:, a:b] & sel[:, None]
+        if bool(left.any()):
+            pts, tiles = _rows_and_tiles(left)
+            problems.append(f"{tag} {name}: {int(left.sum())} words never written, in {pts.numel()} of {p} points (first {pts[:4].tolist()}), tiles {tiles[:8]}")
+        err = (got[:, a:b].double() - want).abs()
+        over = ~(err <= bound) & sel[:, None] & ~left                 # (a NaN is over)
+        judged = err[sel & ~left.any(1)]
+        worst = float(judged.nan_to_num(nan=float("inf")).max()) if judged.numel() else 0.0
+        print(f"{TAG} {tag} {name}: err {worst:.3e}, D {d:.3e}, err / D {worst / d if d else float('inf'):.2f}, err / bound {worst / bound:.2f}, "
+              f"range [{float(want.min()):.4g}, {float(want.max()):.4g}]" + ("" if rows is None else f", {int(sel.sum())} of {p} points"))
+        if bool(over.any()):
+            pts, tiles = _rows_and_tiles(over)
+            problems.append(f"{tag} {name}: |err| {worst:.3e} > {bound:.3e} = {GROUP_FACTORS.get(name, YARDSTICK_FACTOR):g} x {d:.3e} + 2^-21 x {float(want.abs().max()):.4g}; "
+                            f"{int(over.sum())} values over, in {pts.numel()} of {p} points (first {pts[:4].tolist()}), tiles {tiles[:8]}")
+        out[name] = (worst, d, bound)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the kernels, into a caller-owned view
+# ---------------------------------------------------------------------------------------------------------------------
+class RawBuffer:
+    """[GUARD words | ``offset`` words | p x ch rows | GUARD words] of int32, every word the sentinel; ``rows`` is the fp32 view the
+    kernel writes.  The allocation starts on a sixteen-byte boundary, so ``offset`` = 1 puts the rows four bytes off one."""
+
+    def __init__(self, p, ch, device, offset=0):
+        self.first, self.count = GUARD + offset, p * ch
+        self.buf = torch.full((self.first + self.count + GUARD,), fs.SENTINEL, dtype=torch.int32, device=device)
+        assert self.buf.data_ptr() % 16 == 0
+        self.rows = self.buf[self.first: self.first + self.count].view(torch.float32).view(p, ch)
+        assert self.rows.data_ptr() % 16 == (4 * offset) % 16
+
+    def guards_intact(self):
+        return bool((self.buf[:self.first] == fs.SENTINEL).all()) and bool((self.buf[self.first + self.count:] == fs.SENTINEL).all())
+
+    def words(self):
+        return self.buf[self.first: self.first + self.count].cpu()
+
+
+def desc_of(variant, classes, precision=None):
+    ssr = variant == "ssr"
+    return _capi.net_desc(_capi.VARIANT_SSR if ssr else _capi.VARIANT_OBJECT, classes, 10, 4, 10.0 if ssr else 1.0,
+                          _capi.PREC_F16X3 if precision is None else precision)
+
+
+def flags_of(endpoint=False, gate_colour=False, gate_probe=False):
+    return (kernels.FLAG_ENDPOINT if endpoint else 0) | (kernels.FLAG_GATE_COLOUR if gate_colour else 0) | (kernels.FLAG_GATE_PROBE if gate_probe else 0)
+
+
+def launch(desc, packed, rays, z, flags, raw_view, probe_out=None):
+    """inerf_encode_mlp_probed through the C ABI with the workspace inerf_encode_mlp_workspace_bytes asks for (under the environment
+    of the moment: the form is chosen there), into ``raw_view`` [n * s, ch]; the status word as an int, synchronised."""
+    lib = _capi.lib()
+    dev = rays.device
+    n, s = z.shape
+    assert tuple(raw_view.shape) == (n * s, lib.inerf_raw_channels(desc, flags, 1)) and raw_view.is_contiguous()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.inerf_encode_mlp_workspace_bytes(desc, n, s, flags))
+        if ws_bytes < 0:
+            _capi.check(ws_bytes, "inerf_encode_mlp_workspace_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+        rc = lib.inerf_encode_mlp_probed(desc, ptr(packed), ptr(rays), ptr(z), n, s, flags, ptr(raw_view), ptr(status), 0, ptr(ws), ws_bytes,
+                                         ptr(probe_out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    _capi.check(rc, "inerf_encode_mlp_probed")
+    torch.cuda.synchronize(dev)
+    return int(status)

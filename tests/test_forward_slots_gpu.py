@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import _forward_slots as fs
+import _raw_rows as rr
 import oracle
 from intrinsicnerf_amd import _capi, kernels, packing
 
@@ -210,7 +211,8 @@ def test_every_slot_point_for_point_against_fp64(variant, classes, endpoint, for
     fp32 sine's error, which knows nothing of the identity columns' |x| - and passes through the second term, the split's own 2^-22 |x|);
     fragment slots: the padding
     rows of the last tile hold the last point's halves and no half of the whole-tile range is unwritten; the row-format slot
-    (semh): every row of a point written.  act_max is not below the largest value any slot decodes to; status stays 0."""
+    (semh): every row of a point written.  act_max is not below the largest value any slot decodes to; status stays 0.  The raw rows
+    of the same launch: every channel group at the same yardstick (tests/_raw_rows.py judge; figures in tests/test_raw_rows_gpu.py)."""
     case = request.node.callspec.id
     print()                                        # (under -s the figures start on a line of their own)
     dev = torch.device("cuda:0")
@@ -256,6 +258,8 @@ def test_every_slot_point_for_point_against_fp64(variant, classes, endpoint, for
     print(f"{TAG} slots {case}: act_max {act_max!r}, largest decoded |value| {largest!r}, status {status}")
     if not act_max >= largest:
         problems.append(f"act_max {act_max!r} is below the largest decoded |value| {largest!r}")
+    # the same launch's raw rows, one layer behind the last slots: per channel group at the same yardstick (tests/_raw_rows.py)
+    rr.judge(raw.reshape(p, -1), want64["raw"], want32["raw"], rr.groups(variant, classes, endpoint), f"slots {case}", problems)
     assert status == 0
     assert bool(torch.isfinite(raw).all())
     assert not problems, "; ".join(problems)
