@@ -109,11 +109,12 @@ def state_dict_spec(variant: str, n_classes: int = 0, l_xyz: int = 10, l_dir: in
     return spec
 
 
-def make_state_dict(variant: str, n_classes: int = 0, seed: int = 0, dtype=torch.float32) -> Dict[str, Tensor]:
+def make_state_dict(variant: str, n_classes: int = 0, seed: int = 0, dtype=torch.float32,
+                    l_xyz: int = 10, l_dir: int = 4) -> Dict[str, Tensor]:
     """Default-``nn.Linear``-style init, U(-1/sqrt(fan_in), 1/sqrt(fan_in)), from a torch generator."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for key, shape in state_dict_spec(variant, n_classes):
+    for key, shape in state_dict_spec(variant, n_classes, l_xyz, l_dir):
         if key.endswith(".weight"):
             fan_in = shape[1]
         bound = 1.0 / np.sqrt(fan_in)

@@ -59,10 +59,11 @@ def split(p):
     return p // s, s
 
 
-def weights(variant, classes, kind):
+def weights(variant, classes, kind, l_xyz=10, l_dir=4):
     """A fresh state dict: ``plain`` - oracle.make_state_dict(seed 11); ``sharp`` - the same with the output layers' WEIGHTS (biases
-    untouched) times SHARP_GAINS.  (``case_weights`` adds the per-case shift of alpha_linear.bias.)"""
-    sd = oracle.make_state_dict(variant, classes, seed=WEIGHT_SEED)
+    untouched) times SHARP_GAINS.  (``case_weights`` adds the per-case shift of alpha_linear.bias.)  ``l_xyz`` / ``l_dir``: the encodings' band
+    counts (the same init over that description's shapes)."""
+    sd = oracle.make_state_dict(variant, classes, seed=WEIGHT_SEED, l_xyz=l_xyz, l_dir=l_dir)
     if kind == "sharp":
         for group, layer in output_layers(variant, classes).items():
             sd[layer + ".weight"] = sd[layer + ".weight"] * SHARP_GAINS[group]
@@ -103,40 +104,41 @@ def _centre_sharp(variant, classes, sd, slots64):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(variant, classes, endpoint, p, kind):
+def _case(variant, classes, endpoint, p, kind, l_xyz=10, l_dir=4):
     ssr = variant == "ssr"
     n, s = split(p)
     rays, z = fs.rays_and_depths(n, s, seed=p % 1000, origin_scale=3.0 if ssr else 1.0)
     div = 10.0 if ssr else 1.0
-    sd = weights(variant, classes, kind)
-    slots64 = fs.reference_slots(fs.make_module(variant, classes, sd), rays, z, div, endpoint)
+    sd = weights(variant, classes, kind, l_xyz, l_dir)
+    make = functools.partial(fs.make_module, variant, classes, l_xyz=l_xyz, l_dir=l_dir)
+    slots64 = fs.reference_slots(make(sd), rays, z, div, endpoint)
     if kind == "sharp" and p >= 2:     # (one point has no median to split at: it keeps the gains alone, and sigma its natural magnitude)
         _centre_sharp(variant, classes, sd, slots64)
         # the output layers alone have changed: the rows are the heads on the same last slots (test_forward_slots_cpu.py: bit for bit the module's)
-        slots64["raw"] = fs.heads_from_slots(fs.make_module(variant, classes, sd), slots64, endpoint)
-    slots32 = fs.reference_slots(fs.make_module(variant, classes, sd), rays, z, div, endpoint, dtype=torch.float32)
+        slots64["raw"] = fs.heads_from_slots(make(sd), slots64, endpoint)
+    slots32 = fs.reference_slots(make(sd), rays, z, div, endpoint, dtype=torch.float32)
     keep = ("raw",) + (LAST_SLOTS if p <= KEEP_SLOTS_UP_TO else ())
     return {"sd": sd, "rays": rays, "z": z, "slots64": {k: slots64[k] for k in keep}, "raw32": slots32["raw"]}
 
 
-def case_weights(variant, classes, endpoint, p, kind):
+def case_weights(variant, classes, endpoint, p, kind, l_xyz=10, l_dir=4):
     """The state dict of one case (a copy): ``weights`` and, ``sharp``, the per-case centring of _centre_sharp."""
-    return {k: t.clone() for k, t in _case(variant, classes, endpoint, p, kind)["sd"].items()}
+    return {k: t.clone() for k, t in _case(variant, classes, endpoint, p, kind, l_xyz, l_dir)["sd"].items()}
 
 
-def reference(variant, classes, endpoint, p, kind):
+def reference(variant, classes, endpoint, p, kind, l_xyz=10, l_dir=4):
     """(rays, z, raw64, raw32) of one case on the CPU - computed once, shared by the forms, left alone."""
-    c = _case(variant, classes, endpoint, p, kind)
+    c = _case(variant, classes, endpoint, p, kind, l_xyz, l_dir)
     return c["rays"], c["z"], c["slots64"]["raw"], c["raw32"]
 
 
-def last_slots(variant, classes, endpoint, p, kind):
+def last_slots(variant, classes, endpoint, p, kind, l_xyz=10, l_dir=4):
     """{slot: fp64 value} of h7, as1h, vh, semh (and "raw") of a case of at most KEEP_SLOTS_UP_TO points."""
-    return _case(variant, classes, endpoint, p, kind)["slots64"]
+    return _case(variant, classes, endpoint, p, kind, l_xyz, l_dir)["slots64"]
 
 
-def module(variant, classes, endpoint, p, kind):
-    return fs.make_module(variant, classes, case_weights(variant, classes, endpoint, p, kind))
+def module(variant, classes, endpoint, p, kind, l_xyz=10, l_dir=4):
+    return fs.make_module(variant, classes, case_weights(variant, classes, endpoint, p, kind, l_xyz, l_dir), l_xyz, l_dir)
 
 
 def bound_of(raw64, raw32, name, span):
@@ -206,9 +208,9 @@ class RawBuffer:
         return self.buf[self.first: self.first + self.count].cpu()
 
 
-def desc_of(variant, classes, precision=None):
+def desc_of(variant, classes, precision=None, l_xyz=10, l_dir=4):
     ssr = variant == "ssr"
-    return _capi.net_desc(_capi.VARIANT_SSR if ssr else _capi.VARIANT_OBJECT, classes, 10, 4, 10.0 if ssr else 1.0,
+    return _capi.net_desc(_capi.VARIANT_SSR if ssr else _capi.VARIANT_OBJECT, classes, l_xyz, l_dir, 10.0 if ssr else 1.0,
                           _capi.PREC_F16X3 if precision is None else precision)
 
 

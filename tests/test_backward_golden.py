@@ -296,7 +296,7 @@ def _torch_reference_grads(module, embed, embed_d, rays, z, cot, endpoint=False,
         # the SSR encoding's x / 10 (semantic_nerf.py:64) belongs to the positions too: an fp32 true division (done on the
         # CPU: torch's GPU kernel multiplies by the reciprocal), then an embedder without a divisor
         from intrinsicnerf_amd import ssr
-        embed = ssr.get_embedder(10, 0, scalar_factor=1)[0]
+        embed = ssr.get_embedder(embed.n_freqs, 0, scalar_factor=1)[0]      # (the band count of the embedder passed in)
         pts = (pts.cpu() / sf).to(pts.device)
     pts, rays = pts.to(dtype), rays.to(dtype)
     emb = torch.cat([embed(pts.reshape(-1, 3)), embed_d(rays[:, None, 8:11].expand(pts.shape).reshape(-1, 3))], -1)
@@ -481,7 +481,10 @@ def test_network_backward_splits_large_batches(monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("p,m,n", [(64, 256, 256), (1000, 256, 256), (12345, 256, 64), (777, 128, 256), (4097, 128, 32), (70001, 256, 256),
-                                   (44800, 256, 64), (40001, 128, 32), (30000, 128, 256), (50000, 256, 128)])    # several tiles per workgroup, every shape
+                                   (44800, 256, 64), (40001, 128, 32), (30000, 128, 256), (50000, 256, 128),    # several tiles per workgroup
+                                   # the other three of launch_rows' eight tile shapes - 128 x 128 is semantic_linear.1's for every scene
+                                   # of at most 128 classes - at one tile and a point, and at a ragged 65th tile
+                                   (65, 128, 128), (4097, 128, 128), (65, 128, 64), (4097, 128, 64), (65, 256, 32), (4097, 256, 32)])
 def test_weight_gradient_kernel_vs_fp64(p, m, n):
     """G^T X and the column sums of G from the split-K MFMA kernel against an fp64 product: ragged point counts, gradients
     spanning four decades, every supported tile shape; also with operands that are column-aligned views of wider buffers."""

@@ -349,8 +349,24 @@ def test_ssr_semantic_head_forms_agree(c, precision, monkeypatch):
     assert_maps_close(out["t128"][..., 11:].cpu().numpy(), out["wave"][..., 11:].cpu().numpy(), 1e-5, 1e-6, "logits, 128-point tile vs per-wave head")
 
 
-@pytest.mark.parametrize("n,s", [(1, 64), (3, 1), (1, 191), (33, 64), (1000, 192), (4099, 192), (32768, 64)])
-def test_object_kernel_tile_forms_are_bit_identical(n, s, precision, monkeypatch):
+TILE_FORM_CASES = [(1, 64, (10, 4)), (3, 1, (10, 4)), (1, 191, (10, 4)), (33, 64, (10, 4)), (1000, 192, (10, 4)), (4099, 192, (10, 4)),
+                   (32768, 64, (10, 4)), (33, 64, (6, 2))]          # the last: a reduced encoding (the pad columns start at 39 / 15)
+
+
+def _enc_ids(cases):
+    return [f"{n}-{s}" if enc == (10, 4) else f"{n}-{s}-x{enc[0]}d{enc[1]}" for n, s, enc in cases]
+
+
+def _object_weights(enc, seed, rays):
+    """The curated weights of the tile-form tests; at a reduced encoding the same closed-form 1/f weights over that description's
+    shapes (without the density calibration, which probes the default description)."""
+    if enc == (10, 4):
+        return oracle.calibrated_lcg_weights("object", 0, seed, rays)[0]
+    return oracle.lcg_state_dict("object", 0, seed=seed, sigma_gain_log2=5, freq_decay=True, l_xyz=enc[0], l_dir=enc[1])
+
+
+@pytest.mark.parametrize("n,s,enc", TILE_FORM_CASES, ids=_enc_ids(TILE_FORM_CASES))
+def test_object_kernel_tile_forms_are_bit_identical(n, s, enc, precision, monkeypatch):
     """The object-level inference kernel's forms - 128-point tile (k_encode_mlp_f16x3_t128, the default since round 6) and
     64-point tile with two workgroups per CU (k_encode_mlp_f16x3_dual, ``INERF_F16_KERNEL=dual``), and the 128-point tile's
     pipelined trunk (``INERF_F16_KERNEL=pp``) - sum every output element in
@@ -360,13 +376,13 @@ def test_object_kernel_tile_forms_are_bit_identical(n, s, precision, monkeypatch
     if precision != "f16x3":
         pytest.skip("forms of the default f16x3 kernel")
     dev = _dev()
-    cfg = oracle.RenderConfig(variant="object", n_samples=s, n_importance=0)
+    cfg = oracle.RenderConfig(variant="object", n_samples=s, n_importance=0, l_xyz=enc[0], l_dir=enc[1])
     g = torch.Generator().manual_seed(1000 * n + s)
     o = torch.tensor([[2.5, 1.5, 2.0]]).expand(n, 3)
     d = -o / o.norm(dim=-1, keepdim=True) + 0.2 * torch.randn(n, 3, generator=g)
     rays = torch.cat([o, d, 2 * torch.ones(n, 1), 6 * torch.ones(n, 1), d / d.norm(dim=-1, keepdim=True)], -1).contiguous()
     z = torch.sort(torch.rand(n, s, generator=g) * 4 + 2, -1)[0]
-    sd, _ = oracle.calibrated_lcg_weights("object", 0, 40, rays[:256])
+    sd = _object_weights(enc, 40, rays[:256])
     out = {}
     for form in ("t128", "dual", "pp"):      # pp: the 128-point tile with the pipelined trunk (mlp_f16_pp.h; opt-in, measured slower)
         monkeypatch.setenv("INERF_F16_KERNEL", form)
@@ -583,9 +599,12 @@ def test_empty_batches():
     assert tuple(ret["rgb_map"].shape) == (0, 3) and tuple(ret["raw"].shape) == (0, 192, 11)
 
 
+PARKED_CASES = [(3, 1, (10, 4)), (33, 64, (10, 4)), (700, 192, (10, 4)), (33, 64, (6, 2))]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,s", [(3, 1), (33, 64), (700, 192)])
-def test_parked_encoding_equals_the_second_encoder_pass(n, s, precision, monkeypatch):
+@pytest.mark.parametrize("n,s,enc", PARKED_CASES, ids=_enc_ids(PARKED_CASES))
+def test_parked_encoding_equals_the_second_encoder_pass(n, s, enc, precision, monkeypatch):
     """INERF_ENC_CACHE=1: the 128-point tile parks the tile's position encoding in the caller's workspace for the skip layer
     (inerf_encode_mlp_ws / _chunked / inerf_render_rays); by default, and without a workspace (inerf_encode_mlp), it evaluates the encoder a
     second time (run_nerf_helpers.py:290-291: cat([input_pts, h])).  Same bits."""
@@ -594,14 +613,14 @@ def test_parked_encoding_equals_the_second_encoder_pass(n, s, precision, monkeyp
     if precision != "f16x3":
         pytest.skip("a form of the default f16x3 kernel")
     dev = _dev()
-    cfg = oracle.RenderConfig(variant="object", n_samples=s, n_importance=0)
+    cfg = oracle.RenderConfig(variant="object", n_samples=s, n_importance=0, l_xyz=enc[0], l_dir=enc[1])
     g = torch.Generator().manual_seed(7 * n + s)
     o = torch.tensor([[2.5, 1.5, 2.0]]).expand(n, 3)
     d = -o / o.norm(dim=-1, keepdim=True) + 0.2 * torch.randn(n, 3, generator=g)
     rays = torch.cat([o, d, 2 * torch.ones(n, 1), 6 * torch.ones(n, 1), d / d.norm(dim=-1, keepdim=True)], -1).contiguous().to(dev)
     z = torch.sort(torch.rand(n, s, generator=g) * 4 + 2, -1)[0].to(dev)
-    sd, _ = oracle.calibrated_lcg_weights("object", 0, 40, rays[:256].cpu())
-    desc = _capi.net_desc(_capi.VARIANT_OBJECT, 0, 10, 4, 1.0, _capi.PREC_F16X3)
+    sd = _object_weights(enc, 40, rays[:256].cpu())
+    desc = _capi.net_desc(_capi.VARIANT_OBJECT, 0, enc[0], enc[1], 1.0, _capi.PREC_F16X3)
     packed = _packed(cfg, sd)
     lib = _capi.lib()
     monkeypatch.delenv("INERF_F16_KERNEL", raising=False)

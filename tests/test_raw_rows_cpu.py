@@ -34,13 +34,15 @@ SHARP_CASES = [("object", 0, False, 703), ("object", 0, False, 65), ("ssr", 28, 
                ("ssr", 0, False, 65), ("ssr", 5, True, 147)]
 # the forward-slots module's cases at those sizes (its raw rows are judged with the ``plain`` weights)
 PLAIN_CASES = [("object", 0, False, 703), ("object", 0, False, 65), ("ssr", 28, False, 703), ("ssr", 0, False, 65), ("ssr", 5, True, 147)]
-CASES = [c + ("sharp",) for c in SHARP_CASES] + [c + ("plain",) for c in PLAIN_CASES]
+# reduced encodings (test_raw_rows_gpu.py's last rows): (..., kind, l_xyz, l_dir)
+REDUCED_CASES = [("object", 0, False, p, "sharp", lx, ld) for lx, ld in ((6, 2), (0, 0)) for p in (703, 65)] + [("ssr", 28, False, p, "sharp", 3, 0) for p in (703, 65)]
+CASES = [c + ("sharp",) for c in SHARP_CASES] + [c + ("plain",) for c in PLAIN_CASES] + REDUCED_CASES
 MIN_RATIO = {"plain": 2.0, "sharp": 8.0}
 
 
 def _id(case):
-    variant, classes, endpoint, p, kind = case
-    return f"{variant}{classes if variant == 'ssr' else ''}{'-endpoint' if endpoint else ''}-{p}-{kind}"
+    variant, classes, endpoint, p, kind = case[:5]
+    return f"{variant}{classes if variant == 'ssr' else ''}{'-endpoint' if endpoint else ''}-{p}-{kind}" + (f"-x{case[5]}d{case[6]}" if len(case) > 5 else "")
 
 
 def _plain_tolerance_ratio(err, want):
@@ -68,7 +70,7 @@ def f16_hi_activations(v):
 
 @pytest.mark.parametrize("case", [c for c in CASES if c[4] == "sharp"], ids=_id)
 def test_sharp_inputs_are_what_the_docstrings_say(case):
-    variant, classes, endpoint, p, kind = case
+    variant, classes, endpoint, p, kind = case[:5]
     raw64 = rr.reference(*case)[2]
     g = rr.groups(variant, classes, endpoint)
     sigma = raw64[:, 3]
@@ -97,7 +99,7 @@ def test_no_point_of_the_gated_case_is_undecided():
 
 @pytest.mark.parametrize("case", CASES, ids=_id)
 def test_the_bound_sees_one_dropped_product(case):
-    variant, classes, endpoint, p, kind = case
+    variant, classes, endpoint, p, kind = case[:5]
     _, _, raw64, raw32 = rr.reference(*case)
     slots = rr.last_slots(*case)
     groups = rr.groups(variant, classes, endpoint)
@@ -133,6 +135,25 @@ def test_the_bound_sees_one_dropped_product(case):
             if not ratio >= MIN_RATIO[kind]:
                 low.append(f"{group} without its {what}: {ratio:.2f} x bound")
     assert not low, f"{_id(case)}: the bound would miss a dropped product - " + "; ".join(low)
+
+
+WEIGHT_DIGESTS = {("object", 0): "297b0dfacef27512c26e71d74bc553015393058d790ab193302602986acae728",
+                  ("ssr", 28): "f79cff4819300013d0b16f4fd5225c50375a84257ae7d2d34de241594debb19c"}
+
+
+@pytest.mark.parametrize("variant,classes", list(WEIGHT_DIGESTS))
+def test_default_description_weights_are_the_ones_before_the_encoding_arguments(variant, classes):
+    """oracle.make_state_dict took l_xyz / l_dir for the reduced-encoding cases: at the default description (variant, classes, seed) gives
+    the tensors it gave before - sha256 over names and fp32 bytes in order, recorded from the function without the arguments."""
+    import hashlib
+    import oracle
+    for sd in (oracle.make_state_dict(variant, classes, seed=rr.WEIGHT_SEED),
+               oracle.make_state_dict(variant, classes, seed=rr.WEIGHT_SEED, l_xyz=10, l_dir=4), rr.weights(variant, classes, "plain")):
+        h = hashlib.sha256()
+        for name, t in sd.items():
+            h.update(name.encode())
+            h.update(t.numpy().tobytes())
+        assert h.hexdigest() == WEIGHT_DIGESTS[(variant, classes)]
 
 
 def test_judge_names_the_point_and_the_unwritten_word(capsys):

@@ -19,6 +19,8 @@ Worst figures on an MI355X (profiles/raw_rows.txt has every line), err / D and e
   exact fp32    rgb 2.63 / 0.48, sigma 1.89 / 0.40, albedo 1.99 / 0.26, shading 1.99 / 0.29, residual 2.55 / 0.49, logits 2.09 / 0.36, endpoint 2.06 / 0.27
   slot module   (default-init weights, tests/test_forward_slots_gpu.py) err / bound at most 0.28 (sigma), err / D at most 1.54 but for sigma of its
                 one-point case (8.4: that D is one point's; it passes through the bound's second term at 0.16)
+  reduced encodings  (the 22 cases at (6, 2), (0, 0) and SSR C = 28 at (3, 0); profiles/backward_descs.txt) err / D at most 2.95 (residual, exact
+                fp32 at (0, 0)), err / bound at most 0.67 (sigma, exact fp32, C = 28 at (3, 0), 65 points); the f16x3 forms at most 0.54 (residual, C = 28 at (3, 0), 703 points); no factor raised
 A scratch build without one  w_lo x_hi  product of regop_gemm (csrc/mlp_f16_heads.h) fails every two-workgroup and 128-point case here on
 albedo, shading, residual and rgb - 60, 81 and 160 times the bound, the CPU module's prediction - and passes test_encode_mlp_raw.
 """
@@ -61,17 +63,17 @@ def _points(points):
 
 
 @functools.lru_cache(maxsize=None)
-def _packed(variant, classes, endpoint, p, precision):
+def _packed(variant, classes, endpoint, p, precision, enc=(10, 4)):
     """the case's packed weights on the host, once per format"""
-    return packing.pack_state_dict(rr.desc_of(variant, classes, precision), rr.case_weights(variant, classes, endpoint, p, KIND))
+    return packing.pack_state_dict(rr.desc_of(variant, classes, precision, *enc), rr.case_weights(variant, classes, endpoint, p, KIND, *enc))
 
 
-def _setup(variant, classes, endpoint, p, form):
+def _setup(variant, classes, endpoint, p, form, enc=(10, 4)):
     dev = torch.device("cuda:0")
     precision = _capi.PREC_F32 if form == "f32" else _capi.PREC_F16X3
-    desc = rr.desc_of(variant, classes, precision)
-    rays, z, raw64, raw32 = rr.reference(variant, classes, endpoint, p, KIND)
-    return dev, desc, _packed(variant, classes, endpoint, p, precision).to(dev), rays.to(dev), z.to(dev), raw64, raw32
+    desc = rr.desc_of(variant, classes, precision, *enc)
+    rays, z, raw64, raw32 = rr.reference(variant, classes, endpoint, p, KIND, *enc)
+    return dev, desc, _packed(variant, classes, endpoint, p, precision, enc).to(dev), rays.to(dev), z.to(dev), raw64, raw32
 
 
 def _launch(dev, desc, packed, rays, z, flags, offset=0, probe_out=None):
@@ -90,12 +92,14 @@ def _written(buf, problems, tag):
         problems.append(f"{tag}: the guard words around the rows were written")
 
 
-def _id(variant, classes, endpoint, form, points):
-    return f"{variant}{classes if variant == 'ssr' else ''}{'-endpoint' if endpoint else ''}-{form}-{points}"
+def _id(variant, classes, endpoint, form, points, enc=(10, 4)):
+    return (f"{variant}{classes if variant == 'ssr' else ''}{'-endpoint' if endpoint else ''}-{form}-{points}"
+            + ("" if enc == (10, 4) else f"-x{enc[0]}d{enc[1]}"))
 
 
 def _params(rows):
-    return [pytest.param(*r, id=_id(*r)) for r in rows]
+    """rows of (variant, classes, endpoint, form, points[, (l_xyz, l_dir)]): the encodings default to (10, 4)"""
+    return [pytest.param(*(tuple(r) + ((10, 4),))[:6], id=_id(*r)) for r in rows]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -117,17 +121,20 @@ INFERENCE = (
     + [("ssr", 5, True, form, 147) for form in ("default", "f32")]
     # the persistent loop's second trip, one case per kernel body
     + [("object", 0, False, "dual", "loop-2wg"), ("ssr", 28, False, "default", "loop-2wg"), ("object", 0, False, "single", "loop-1wg"),
-       ("object", 0, False, "default", "loop-t128"), ("ssr", 28, False, "t128", "loop-t128")])
+       ("object", 0, False, "default", "loop-t128"), ("ssr", 28, False, "t128", "loop-t128")]
+    # reduced encodings (the pad columns of the encoding slots start at 39 / 15, 3 / 3 and 21 / 3): every object-level body, the SSR heads
+    + [("object", 0, False, form, p, enc) for enc in ((6, 2), (0, 0)) for form in ("default", "dual", "single", "f32") for p in (703, 65)]
+    + [("ssr", 28, False, form, p, (3, 0)) for form in ("default", "t128", "f32") for p in (703, 65)])
 
 
-@pytest.mark.parametrize("variant,classes,endpoint,form,points", _params(INFERENCE))
-def test_rows_against_fp64(variant, classes, endpoint, form, points, monkeypatch):
+@pytest.mark.parametrize("variant,classes,endpoint,form,points,enc", _params(INFERENCE))
+def test_rows_against_fp64(variant, classes, endpoint, form, points, enc, monkeypatch):
     """inerf_encode_mlp_probed, one launch: rows written, guards intact, status 0, every group within 4 D + 2^-21 max |fp64| of fp64."""
     print()
     p = _points(points)
-    tag = _id(variant, classes, endpoint, form, points) + (f" ({p} points)" if p != points else "")
+    tag = _id(variant, classes, endpoint, form, points, enc) + (f" ({p} points)" if p != points else "")
     _select_form(monkeypatch, form)
-    dev, desc, packed, rays, z, raw64, raw32 = _setup(variant, classes, endpoint, p, form)
+    dev, desc, packed, rays, z, raw64, raw32 = _setup(variant, classes, endpoint, p, form, enc)
     buf, status = _launch(dev, desc, packed, rays, z, rr.flags_of(endpoint))
     problems = []
     _written(buf, problems, tag)
@@ -185,10 +192,10 @@ def test_gated_rows_against_fp64(probe, form, monkeypatch, request):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. the training forward
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("variant,classes,endpoint,form,points", _params([
+@pytest.mark.parametrize("variant,classes,endpoint,form,points,enc", _params([
     ("object", 0, False, "default", 703), ("object", 0, False, "single", 703), ("object", 0, False, "train-t128", 703),
     ("ssr", 28, False, "default", 703), ("ssr", 28, False, "single", 703), ("ssr", 5, True, "default", 147)]))
-def test_training_forward_rows_against_fp64(variant, classes, endpoint, form, points, monkeypatch):
+def test_training_forward_rows_against_fp64(variant, classes, endpoint, form, points, enc, monkeypatch):
     """inerf_encode_mlp_train (the saving forms of the same tails): the same four checks on its raw rows."""
     print()
     tag = "train " + _id(variant, classes, endpoint, form, points)

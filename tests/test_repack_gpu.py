@@ -13,14 +13,25 @@ import oracle
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("variant,c", [("object", 0), ("ssr", 28), ("ssr", 101), ("ssr", 0)])
-def test_hip_repack_is_bit_identical_to_the_host_packer(variant, c, monkeypatch):
-    from intrinsicnerf_amd import _capi, packing
-    dev = torch.device("cuda:0")
-    desc = _capi.net_desc(_capi.VARIANT_SSR if variant == "ssr" else _capi.VARIANT_OBJECT, c, 10, 4, 10.0 if variant == "ssr" else 1.0,
+def _desc(variant, c, l_xyz=10, l_dir=4):
+    from intrinsicnerf_amd import _capi
+    return _capi.net_desc(_capi.VARIANT_SSR if variant == "ssr" else _capi.VARIANT_OBJECT, c, l_xyz, l_dir, 10.0 if variant == "ssr" else 1.0,
                           precision=_capi.PREC_F16X3)
+
+
+CASES = [("object", 0, 10, 4), ("ssr", 28, 10, 4), ("ssr", 101, 10, 4), ("ssr", 0, 10, 4),
+         # reduced encodings (where the pad columns start) and the class edges 129 / 240
+         ("object", 0, 6, 2), ("object", 0, 0, 0), ("ssr", 240, 6, 2), ("ssr", 129, 10, 4)]
+
+
+@pytest.mark.parametrize("variant,c,l_xyz,l_dir", CASES,
+                         ids=[f"{v}-{c}" if (lx, ld) == (10, 4) else f"{v}-{c}-x{lx}d{ld}" for v, c, lx, ld in CASES])
+def test_hip_repack_is_bit_identical_to_the_host_packer(variant, c, l_xyz, l_dir, monkeypatch):
+    from intrinsicnerf_amd import packing
+    dev = torch.device("cuda:0")
+    desc = _desc(variant, c, l_xyz, l_dir)
     for seed in (3, 4):
-        sd = oracle.make_state_dict(variant, c, seed=seed)
+        sd = oracle.make_state_dict(variant, c, seed=seed, l_xyz=l_xyz, l_dir=l_dir)
         if seed == 4:
             sd["pts_linears.2.weight"] = sd["pts_linears.2.weight"] * 0.0          # an all-zero GEMM: scale 1
             sd["feature_linear.weight"] = sd["feature_linear.weight"] * 1000.0     # moves the common scale of the d h7 group
@@ -33,7 +44,7 @@ def test_hip_repack_is_bit_identical_to_the_host_packer(variant, c, monkeypatch)
             got = packer(sd_dev)                       # the library's inerf_repack
             twin = packer._repack_torch(sd_dev)        # its framework twin (what CPU tensors take)
             torch.cuda.synchronize()
-            assert torch.equal(host.view(torch.int32), got.cpu().view(torch.int32)), (variant, c, seed, backward, "hip vs host")
+            assert torch.equal(host.view(torch.int32), got.cpu().view(torch.int32)), (variant, c, l_xyz, l_dir, seed, backward, "hip vs host")
             differing = int((twin.view(torch.int16) != got.view(torch.int16)).sum())
-            print(f"{variant} C={c} seed {seed} {'bwd' if backward else 'fwd'}: framework twin differs from the host packer in {differing} of "
+            print(f"{variant} C={c} ({l_xyz}, {l_dir}) seed {seed} {'bwd' if backward else 'fwd'}: framework twin differs from the host packer in {differing} of "
                   f"{2 * got.numel()} halves")
