@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40018
+#define INERF_ABI_VERSION 40019
 
 /* error codes */
 #define INERF_OK              0
@@ -662,6 +662,58 @@ int inerf_cluster_snap_compose(const float* albedo, const float* label, const fl
                                const int32_t* anchor_begin, const float* factor, const float* centers,
                                const int32_t* center_begin, int n_classes, uint32_t flags, unsigned char* out_c,
                                unsigned char* out_edit, float* out_color, void* stream);
+
+/* Scene editing on the device: the edit engine of the reference's GUI (gui.py; gui_obj.py is the same engine) - recolour a
+ * cluster centre, reshape and rescale shading and residual, compose the frame again.
+ *
+ * inerf_edit_params: the edit state both kernel forms read (host struct, passed by pointer, copied at the call).
+ *   edit_centers[Ctot,3] (device, fp32) = the editable copy of inerf_cluster_lookup's `centers`, same layout: rgb_centers of
+ *   gui.py:49-60 (update_color) / :337-352 (reset); shading_mode 0: t_shading(s) = s, 1: s * s (gui.py:490-496);
+ *   residual_mode 0: t_residual(r) = r, 1: (sin(r * pi - pi / 2) + 1) / 2 (gui.py:498-502), pi and pi / 2 rounded to fp32
+ *   first, the accurate sine; shading_scale, residual_scale = global_shading_scale, global_residual_scale (gui.py:478-488).
+ *   Per pixel and channel (gui.py:163, fp32, left to right, no contraction):
+ *     result = ((colour * t_shading(shading)) * shading_scale) + (t_residual(residual) * residual_scale)
+ *   8-bit outputs are to8b as inerf_frame_to_u8: (uint8)(255 * clip(x, 0, 1)), NaN -> 0. */
+typedef struct inerf_edit_params {
+    const float* edit_centers;
+    int32_t shading_mode;
+    int32_t residual_mode;
+    float shading_scale;
+    float residual_scale;
+} inerf_edit_params;
+
+/* inerf_edit_frame: search form, for a frame seen for the first time - cluster_img (gui.py:268-281, :529-540) and
+ *   update_img (gui.py:155-163) in one launch.  Inputs and cluster tables are inerf_cluster_snap_compose's (`centers` is
+ *   replaced by params->edit_centers), and so are the search, its argmin, its NaN rule and its two tile widths:
+ *     colour = edit_centers[center_begin[label] + links[argmin]] - the albedo itself where the label has no cluster
+ *     out_result[n,3] (u8) = to8b(result); out_c[n,3] (u8, optional) = to8b(colour) (view mode 1, gui.py:171-173);
+ *     out_result_f32[n,3] (optional) = result; out_slot[n] (int32, optional) = center_begin[label] + links[argmin], the
+ *     global row of the pixel's centre, or -1 where the pixel keeps its albedo (label outside [0, K), class without cluster).
+ *   INERF_E_INVALID: a null required pointer (params and its edit_centers included), n_pixels < 0, row_stride < 3,
+ *   n_classes < 1, a mode outside {0, 1}, anchors not 16-byte aligned, any other pointer - out_result and out_c included -
+ *   not 4-byte aligned; n_pixels == 0 is INERF_OK whatever the pointers; INERF_E_UNSUPPORTED: more than 2^31 - 1 blocks. */
+int inerf_edit_frame(const float* albedo, const float* label, const float* shading, const float* residual, int64_t row_stride,
+                     int64_t n_pixels, const float* anchors, const int32_t* links, const int32_t* anchor_begin,
+                     const float* factor, const int32_t* center_begin, int n_classes, uint32_t flags,
+                     const inerf_edit_params* params, unsigned char* out_result, unsigned char* out_c, float* out_result_f32,
+                     int32_t* out_slot, void* stream);
+
+/* inerf_edit_recompose / inerf_edit_recompose_u8: cached form, every later tick of update_img (gui.py:155-163) - no search.
+ *   colour = slot[p] >= 0 ? edit_centers[slot[p]] : albedo[p]; then the same transfers, scales and outputs as above.
+ *   Sources: fp32 pack columns as above (albedo 3, shading 1, residual 3 floats, consecutive pixels row_stride floats apart),
+ *   or the three 8-bit planes load_all_image reads (gui.py:216-228) - albedo[n,3], shading[n], residual[n,3] - converted as
+ *   (float)v / 255.0f, IEEE division = numpy's (v / 255.).astype(float32) for all 256 values.
+ *   n_pixels may span a whole sequence of frames back to back.  8-bit sources and out_result / out_c are taken at ANY byte
+ *   alignment (a frame of an odd pixel count inside a sequence): whole dwords in the middle, bytes at head and tail.
+ *   INERF_E_INVALID: a null required pointer (out_c, out_result_f32 are optional), n_pixels < 0, a mode outside {0, 1},
+ *   row_stride < 3 (fp32 form), slot / fp32 pointers / edit_centers not 4-byte aligned; n_pixels == 0 is INERF_OK whatever
+ *   the pointers; INERF_E_UNSUPPORTED: more than 2^31 - 1 blocks of 2048 pixels. */
+int inerf_edit_recompose(const float* albedo, const float* shading, const float* residual, int64_t row_stride, const int32_t* slot,
+                         int64_t n_pixels, const inerf_edit_params* params, unsigned char* out_result, unsigned char* out_c,
+                         float* out_result_f32, void* stream);
+int inerf_edit_recompose_u8(const unsigned char* albedo, const unsigned char* shading, const unsigned char* residual,
+                            const int32_t* slot, int64_t n_pixels, const inerf_edit_params* params, unsigned char* out_result,
+                            unsigned char* out_c, float* out_result_f32, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Networks outside the fused architecture, and fp32 training batches: one launch per nn.Linear on the fp32 matrix core.

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40018          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40019          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -114,6 +114,12 @@ class DrawArgs(C.Structure):
                 ("noise_std", C.c_float), ("flags", C.c_uint32)]
 
 
+class EditParams(C.Structure):
+    """inerf_edit_params: the edit state of the scene-editing kernels (include/inerf.h, inerf_edit_frame)."""
+    _fields_ = [("edit_centers", C.c_void_p), ("shading_mode", C.c_int32), ("residual_mode", C.c_int32),
+                ("shading_scale", C.c_float), ("residual_scale", C.c_float)]
+
+
 class Ndc(C.Structure):
     """inerf_ndc: the NDC projection's coefficients (include/inerf.h, inerf_gen_rays_ndc)."""
     _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("near_plane", C.c_float)]
@@ -189,6 +195,9 @@ SYMBOLS = {
     "inerf_cluster_fit": (_I, [C.POINTER(ClusterFitArgs), _P]),
     "inerf_frame_subsample": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "inerf_cluster_snap_compose": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _P, _P]),
+    "inerf_edit_frame": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I, _U, C.POINTER(EditParams), _P, _P, _P, _P, _P]),
+    "inerf_edit_recompose": (_I, [_P, _P, _P, _L, _P, _L, C.POINTER(EditParams), _P, _P, _P, _P]),
+    "inerf_edit_recompose_u8": (_I, [_P, _P, _P, _P, _L, C.POINTER(EditParams), _P, _P, _P, _P]),
     "inerf_linear": (_I, [C.POINTER(LinearArgs), _P]),
     "inerf_linear_wgrad_workspace_bytes": (_L, [_L, _I, _I]),
     "inerf_linear_wgrad": (_I, [_P, _L, _I, _P, _L, _I, _L, _P, _P, _I, _P, _L, _P]),

@@ -15,6 +15,7 @@
 
 #include "cluster_search.h"
 #include "layout.h"
+#include "to_u8.h"
 
 namespace inerf {
 
@@ -56,12 +57,6 @@ __global__ __launch_bounds__(256) void k_frame_subsample(const float* __restrict
         for (int c = threadIdx.x; c < n_classes; c += 256)
             if (hist[c]) atomicAdd(&class_counts[c], hist[c]);
     }
-}
-
-// (uint8)(255 * clip(v, 0, 1)): numpy's float32 product, truncation toward zero; NaN -> 0 (k_frame_to_u8)
-__device__ __forceinline__ unsigned to_u8(float v) {
-    const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);             // NaN fails both comparisons and stays NaN
-    return c == c ? (unsigned)(int)__fmul_rn(255.0f, c) : 0u;
 }
 
 struct SnapInputs {               // columns of one [n, row_stride] fp32 tensor (a frame's pack)

@@ -373,6 +373,117 @@ def cluster_snap_compose(tables, pack, albedo_col, shading_col, residual_col, la
     return out, color
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# scene editing (csrc/edit.hip): the edit engine of gui.py.  ``out`` follows cluster_snap_compose's convention - with
+# ``want_c`` a [2, snap_row_bytes(n)] uint8 buffer whose rows are to8b(colour) and to8b(result) (``snap_images``), one
+# buffer for one device->host copy; without it a [1, snap_row_bytes(n)] buffer holding the result alone (``out[-1]``)
+# ---------------------------------------------------------------------------------------------------------------------
+def _edit_params(tables, edit_centers, shading_mode, residual_mode, shading_scale, residual_scale):
+    if not (isinstance(edit_centers, torch.Tensor) and edit_centers.dtype == torch.float32 and edit_centers.is_contiguous()
+            and edit_centers.device == tables.device and tuple(edit_centers.shape) == tuple(tables.centers.shape)):
+        raise ValueError(f"edit_centers must be a contiguous float32 {tuple(tables.centers.shape)} tensor on {tables.device}, like the tables' centers")
+    for name, mode in (("shading_mode", shading_mode), ("residual_mode", residual_mode)):
+        if mode not in (0, 1, False, True):
+            raise ValueError(f"{name} must be 0 or 1, got {mode!r}")
+    return _capi.EditParams(edit_centers.data_ptr(), int(shading_mode), int(residual_mode), float(shading_scale), float(residual_scale))
+
+
+def _edit_outputs(n, device, out, want_c, want_f32):
+    rows, row = (2 if want_c else 1), snap_row_bytes(n)
+    if out is None:
+        out = torch.empty(rows, row, dtype=torch.uint8, device=device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == (rows, row) and out.is_contiguous()
+              and out.device == device):
+        raise ValueError(f"out must be a contiguous [{rows}, {row}] uint8 tensor on {device}")
+    base = out.data_ptr()
+    result_f32 = torch.empty(n, 3, dtype=torch.float32, device=device) if want_f32 else None
+    return out, (C.c_void_p(base) if want_c else None), C.c_void_p(base + (row if want_c else 0)), result_f32
+
+
+def _edit_slots(slot, n, device):
+    if not (isinstance(slot, torch.Tensor) and slot.dtype == torch.int32 and slot.dim() == 1 and slot.shape[0] == n and slot.is_contiguous()
+            and slot.device == device):
+        raise ValueError(f"slot must be a contiguous int32 vector of {n} entries on {device}")
+    return slot
+
+
+def edit_frame(tables, edit_centers, pack, albedo_col, shading_col, residual_col, label_col=-1, shading_mode=0, residual_mode=0,
+               shading_scale=1.0, residual_scale=1.0, out=None, want_c=True, want_f32=False, want_slot=False):
+    """Search form of the edit (``inerf_edit_frame``): ``cluster_snap_compose``'s inputs, the colour read from ``edit_centers``
+    (the editable copy of ``tables.centers``), gui.py:163's transfers and scales.  Returns ``(out, result, slot)``: ``result``
+    [n, 3] fp32 only with ``want_f32``; ``slot`` [n] int32 only with ``want_slot`` - the global row of every pixel's centre in
+    ``edit_centers``, -1 where the pixel keeps its albedo: what ``edit_recompose`` takes instead of a search."""
+    pack = _dev(pack, "pack", (None, None))
+    n, stride = pack.shape
+    if pack.device != tables.device:
+        raise ValueError(f"pack is on {pack.device}, the cluster tables on {tables.device}")
+    labelled = label_col is not None and int(label_col) >= 0
+    for name, col, w in (("albedo", albedo_col, 3), ("shading", shading_col, 1), ("residual", residual_col, 3)) + ((("label", label_col, 1),) if labelled else ()):
+        if not 0 <= int(col) <= stride - w:
+            raise ValueError(f"{name}_col={col} lies outside a row of {stride} floats")
+    params = _edit_params(tables, edit_centers, shading_mode, residual_mode, shading_scale, residual_scale)
+    out, c_ptr, result_ptr, result = _edit_outputs(n, pack.device, out, want_c, want_f32)
+    slot = torch.empty(n, dtype=torch.int32, device=pack.device) if want_slot else None
+    base = pack.data_ptr()
+    at = lambda col: C.c_void_p(base + 4 * int(col))
+    with torch.cuda.device(pack.device):
+        rc = _capi.lib().inerf_edit_frame(
+            at(albedo_col), at(label_col) if labelled else None, at(shading_col), at(residual_col), stride, n, _ptr(tables.anchors),
+            _ptr(tables.links), _ptr(tables.anchor_begin), _ptr(tables.factor), _ptr(tables.center_begin), tables.n_classes,
+            0 if labelled else _capi.CLUSTER_IGNORE_LABEL, C.byref(params), result_ptr, c_ptr, _ptr(result), _ptr(slot), _stream(pack))
+    _capi.check(rc, "inerf_edit_frame")
+    return out, result, slot
+
+
+def edit_recompose(tables, edit_centers, pack, albedo_col, shading_col, residual_col, slot, shading_mode=0, residual_mode=0,
+                   shading_scale=1.0, residual_scale=1.0, out=None, want_c=True, want_f32=False):
+    """Cached form of the edit over fp32 pack columns (``inerf_edit_recompose``): no search - ``slot`` (``edit_frame``'s) selects
+    each pixel's centre.  Returns ``(out, result)`` as ``edit_frame``."""
+    pack = _dev(pack, "pack", (None, None))
+    n, stride = pack.shape
+    if pack.device != tables.device:
+        raise ValueError(f"pack is on {pack.device}, the cluster tables on {tables.device}")
+    for name, col, w in (("albedo", albedo_col, 3), ("shading", shading_col, 1), ("residual", residual_col, 3)):
+        if not 0 <= int(col) <= stride - w:
+            raise ValueError(f"{name}_col={col} lies outside a row of {stride} floats")
+    slot = _edit_slots(slot, n, pack.device)
+    params = _edit_params(tables, edit_centers, shading_mode, residual_mode, shading_scale, residual_scale)
+    out, c_ptr, result_ptr, result = _edit_outputs(n, pack.device, out, want_c, want_f32)
+    base = pack.data_ptr()
+    at = lambda col: C.c_void_p(base + 4 * int(col))
+    with torch.cuda.device(pack.device):
+        rc = _capi.lib().inerf_edit_recompose(at(albedo_col), at(shading_col), at(residual_col), stride, _ptr(slot), n, C.byref(params),
+                                              result_ptr, c_ptr, _ptr(result), _stream(pack))
+    _capi.check(rc, "inerf_edit_recompose")
+    return out, result
+
+
+def edit_recompose_u8(tables, edit_centers, albedo, shading, residual, slot, shading_mode=0, residual_mode=0, shading_scale=1.0,
+                      residual_scale=1.0, out=None, want_c=True, want_f32=False):
+    """Cached form of the edit over the 8-bit planes ``load_all_image`` reads (``inerf_edit_recompose_u8``): ``albedo`` [n, 3],
+    ``shading`` [n], ``residual`` [n, 3] uint8, each ``v / 255`` as numpy rounds it; views into a longer sequence are taken at any
+    byte offset.  Returns ``(out, result)`` as ``edit_frame``."""
+    for name, t in (("albedo", albedo), ("shading", shading), ("residual", residual)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} lives on {t.device}: intrinsicnerf_amd runs only on a HIP device (no CPU / eager fallback exists)")
+        if t.device != tables.device:
+            raise ValueError(f"{name} is on {t.device}, the cluster tables on {tables.device}")
+    n = shading.numel()
+    if shading.dim() != 1 or tuple(albedo.shape) != (n, 3) or tuple(residual.shape) != (n, 3):
+        raise ValueError(f"expected albedo [n, 3], shading [n], residual [n, 3]; got {tuple(albedo.shape)}, {tuple(shading.shape)}, {tuple(residual.shape)}")
+    slot = _edit_slots(slot, n, shading.device)
+    params = _edit_params(tables, edit_centers, shading_mode, residual_mode, shading_scale, residual_scale)
+    out, c_ptr, result_ptr, result = _edit_outputs(n, shading.device, out, want_c, want_f32)
+    u8 = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(shading.device):
+        rc = _capi.lib().inerf_edit_recompose_u8(u8(albedo), u8(shading), u8(residual), _ptr(slot), n, C.byref(params), result_ptr, c_ptr,
+                                                 _ptr(result), _stream(shading))
+    _capi.check(rc, "inerf_edit_recompose_u8")
+    return out, result
+
+
 def _new_status(like):
     return torch.zeros(1, dtype=torch.int32, device=like.device)
 
