@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40019
+#define INERF_ABI_VERSION 40020
 
 /* error codes */
 #define INERF_OK              0
@@ -1032,6 +1032,94 @@ int inerf_occupancy_grid(const inerf_net_desc* net, const float* packed_weights,
                          const float* scale /*[host] 3*/, const float* transform /*[host] 12*/, float dist, int64_t first_point,
                          int64_t n_points, float* occ_out /*[n_points]*/, float* sigma_out /*[n_points] or NULL*/,
                          int32_t* status, int64_t status_points, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Validation metrics (csrc/eval.hip): the label and entropy maps of a rendered frame (SSR/training/trainer.py:1244-1245) and the
+ * accumulators behind calculate_segmentation_metrics, calculate_depth_metrics and img2mse (SSR/training/training_utils.py:58-124).
+ * The host finishing (normalised rows, nanmean, ious, means, square roots) is a few float64 lines on C * C + 14 numbers and stays
+ * with the caller (intrinsicnerf_amd/evaluation.py).
+ * ------------------------------------------------------------------------------------------- */
+
+/* label[i * label_stride] = the LOWEST index that attains the maximum of logits[i * logits_stride + 0 .. n_classes), as a float;
+ * entropy[i * entropy_stride] = -sum_c p_c log p_c of the row's softmax.  Either output may be NULL; each has an element stride
+ * of its own, so it can be a column of a frame's pack.
+ *   Label: equals the reference's argmax(softmax(x)) whenever the runner-up is bitwise equal to the maximum or below it by more
+ *   than fp32 rounding of the softmax can hide; where two logits differ by less than ~1e-7 torch may answer a lower index because
+ *   the softmax values round equal - rounding noise of the reference, not reproduced.
+ *   A row that holds a NaN, or whose maximum is not finite: label 0, entropy NaN (as torch).  A row with a -inf entry and a finite
+ *   maximum: its label, entropy NaN (-(-inf) * 0, as torch).
+ *   Entropy: max-subtracted, accurate expf, the two sums and log S - T / S in fp64 (csrc/eval.hip's header comment).
+ * 1 <= n_classes <= INERF_MAX_CLASSES, else INERF_E_UNSUPPORTED; n < 0 or a stride smaller than its width (logits_stride <
+ * n_classes, an output stride < 1): INERF_E_INVALID.  n == 0 is a no-op.  Nothing is allocated, synchronised or read on the host. */
+int inerf_sem_maps(const float* logits, int64_t logits_stride, int64_t n, int n_classes, float* label, int64_t label_stride,
+                   float* entropy, int64_t entropy_stride, void* stream);
+
+/* counts[n_classes * n_classes + INERF_EVAL_COUNTS] (int64): the confusion table, row = true label and column = predicted label
+ * as sklearn.metrics.confusion_matrix lays it out, then these counters */
+#define INERF_EVAL_COUNTS 8
+#define INERF_EVAL_N_NOT_IGNORED    0   /* pixels whose true label != ignore_label                       */
+#define INERF_EVAL_N_PIXELS         1   /* pixels seen by the depth group                                 */
+#define INERF_EVAL_N_PRED_POSITIVE  2   /* ... with depth_pred > 0  ("complete")                         */
+#define INERF_EVAL_N_MASK           3   /* ... inside mask = (trgt < 10) * (trgt > 0) * (pred > 0)       */
+#define INERF_EVAL_R1               4   /* masked pixels with max(t / p, p / t) < 1.25                    */
+#define INERF_EVAL_R2               5   /* ... < 1.5625                                                   */
+#define INERF_EVAL_R3               6   /* ... < 1.953125                                                 */
+#define INERF_EVAL_N_RGB            7   /* rgb values compared (3 per pixel)                              */
+/* sums[INERF_EVAL_SUMS] (double): over the masked pixels, and over every rgb value */
+#define INERF_EVAL_SUMS 6
+#define INERF_EVAL_ABS_REL      0
+#define INERF_EVAL_ABS_DIFF     1
+#define INERF_EVAL_SQ_REL       2
+#define INERF_EVAL_SQ_DIFF      3
+#define INERF_EVAL_SQ_LOG_DIFF  4
+#define INERF_EVAL_RGB_SQ       5
+
+/* One pass over n pixels that ADDS into `counts` and `sums`, which the caller owns, zeroes and keeps on the device across frames.
+ * Three optional groups:
+ *   labels (true_label != NULL): the predicted label is pred_label (a float column) or, when `logits` is non-NULL, derived from
+ *     the logits by inerf_sem_maps' device code in this launch - out_label / out_entropy (each optional) are then written as
+ *     inerf_sem_maps writes them, also without a true label.  true_label holds floats as the trainer keeps them (label - 1,
+ *     void = ignore_label).  A pixel counts as not ignored when true != ignore_label, and enters the table only if, besides, both
+ *     labels are integers in [0, n_classes) - a non-integer, a NaN or a label >= n_classes is dropped, as sklearn's labels= does.
+ *   depth (depth_pred != NULL, depth_trgt required): training_utils.py:96-109 per pixel in fp32, unfused, in the reference's order:
+ *     a = |p - t|, a / t, a * a, (a * a) / t, (logf(p) - logf(t))^2, max(t / p, p / t) against 1.25f, 1.5625f, 1.953125f; with IEEE
+ *     division every term but the logarithm has numpy's bits and every count is exact.
+ *   rgb (rgb_pred != NULL, rgb_trgt required, 3 floats per pixel `stride` floats apart): (x - y)^2 in fp32 per value.
+ * Every stride is in floats.  Bit-identical from run to run: counts through integer atomics (the table privatised in LDS up to 64
+ * classes, global beyond), the fp64 sums through fixed trees into one partial row per workgroup in `workspace`
+ * (inerf_eval_workspace_bytes(n) bytes, else INERF_E_WORKSPACE) and a second launch that adds the rows in index order.  No
+ * floating-point atomic, no hand-off between workgroups inside a kernel; the grid depends on n alone.  Errors as inerf_sem_maps
+ * (n_classes is checked whichever groups are given: it sizes `counts`); n == 0 is a no-op; n > 2^31 - 1: INERF_E_UNSUPPORTED.
+ * Capturable into a HIP graph. */
+typedef struct inerf_eval_args {
+    int64_t n;
+    int32_t n_classes;
+    int32_t ignore_label;
+    const float* logits;
+    int64_t logits_stride;
+    const float* pred_label;
+    int64_t pred_label_stride;
+    float* out_label;
+    int64_t out_label_stride;
+    float* out_entropy;
+    int64_t out_entropy_stride;
+    const float* true_label;
+    int64_t true_label_stride;
+    const float* depth_pred;
+    int64_t depth_pred_stride;
+    const float* depth_trgt;
+    int64_t depth_trgt_stride;
+    const float* rgb_pred;
+    int64_t rgb_pred_stride;
+    const float* rgb_trgt;
+    int64_t rgb_trgt_stride;
+    int64_t* counts;
+    double* sums;
+    void* workspace;
+    int64_t workspace_bytes;
+} inerf_eval_args;
+int64_t inerf_eval_workspace_bytes(int64_t n);
+int inerf_eval_accumulate(const inerf_eval_args* args, void* stream);
 
 #ifdef __cplusplus
 }

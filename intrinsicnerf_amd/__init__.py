@@ -4,6 +4,7 @@
   ssr            drop-in for SSR/ + train_SSR_main.py's render path (SSRRenderMixin, Semantic_NeRF, ...)
   losses         the trainers' loss terms, one forward and one backward launch (compute_intrinsic_loss, *_step_loss)
   geometry       mesh extraction's query lattice and occupancy grid (grid_within_bound, make_3D_grid, occupancy_grid)
+  evaluation     the trainer's validation metrics on the device (calculate_segmentation_metrics, calculate_depth_metrics, FrameEvaluator)
   optim          the trainers' optimizer.step(): Adam as one launch of the library (optim.Adam)
   draws          the training step's random variates drawn in the kernels (DrawState; opt-in)
   kernels        tensor-level launchers of the C ABI (include/inerf.h, libinerf.so)
@@ -17,6 +18,7 @@ device the render entry points raise.
 from . import _capi, kernels, packing  # noqa: F401
 from . import object_level, ssr  # noqa: F401
 from . import geometry  # noqa: F401
+from . import evaluation  # noqa: F401
 from . import optim  # noqa: F401
 from . import draws  # noqa: F401
 from .draws import DrawState  # noqa: F401

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40019          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40020          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -125,6 +125,21 @@ class Ndc(C.Structure):
     _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("near_plane", C.c_float)]
 
 
+class EvalArgs(C.Structure):
+    """inerf_eval_args: one accumulate pass of the validation metrics (include/inerf.h, inerf_eval_accumulate)."""
+    _fields_ = [("n", C.c_int64), ("n_classes", C.c_int32), ("ignore_label", C.c_int32),
+                ("logits", C.c_void_p), ("logits_stride", C.c_int64), ("pred_label", C.c_void_p), ("pred_label_stride", C.c_int64),
+                ("out_label", C.c_void_p), ("out_label_stride", C.c_int64), ("out_entropy", C.c_void_p), ("out_entropy_stride", C.c_int64),
+                ("true_label", C.c_void_p), ("true_label_stride", C.c_int64), ("depth_pred", C.c_void_p), ("depth_pred_stride", C.c_int64),
+                ("depth_trgt", C.c_void_p), ("depth_trgt_stride", C.c_int64), ("rgb_pred", C.c_void_p), ("rgb_pred_stride", C.c_int64),
+                ("rgb_trgt", C.c_void_p), ("rgb_trgt_stride", C.c_int64), ("counts", C.c_void_p), ("sums", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+EVAL_COUNTS, EVAL_SUMS = 8, 6
+EVAL_COUNT_NAMES = ("n_not_ignored", "n_pixels", "n_pred_positive", "n_mask", "r1", "r2", "r3", "n_rgb")
+EVAL_SUM_NAMES = ("abs_rel", "abs_diff", "sq_rel", "sq_diff", "sq_log_diff", "rgb_sq")
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -221,6 +236,9 @@ SYMBOLS = {
     "inerf_grid_points": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _L, _L, _P, _P]),
     "inerf_grid_points_host": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _L, _L, _P]),
     "inerf_occupancy_grid": (_I, [C.POINTER(NetDesc), _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _L, _L, _P, _P, _P, _L, _P]),
+    "inerf_sem_maps": (_I, [_P, _L, _L, _I, _P, _L, _P, _L, _P]),
+    "inerf_eval_workspace_bytes": (_L, [_L]),
+    "inerf_eval_accumulate": (_I, [C.POINTER(EvalArgs), _P]),
 }
 
 _lib = None

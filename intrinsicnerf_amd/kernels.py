@@ -1559,3 +1559,171 @@ def batch_ssr(image, depth, semantic, n, rays=None, camera=None, avail=None, ind
     _capi.check(rc, "inerf_batch_assemble")
     out = (out_rays, out_rgb, out_depth, out_sem, out_avail)
     return out + (idx,) if return_indices else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# validation metrics (csrc/eval.hip).  Every float argument is a VIEW, never copied: [n] with any element stride or [n, width]
+# with unit stride along the row and any row stride >= width - a column (range) of a frames.pack_maps pack, or a tensor of its own
+# ---------------------------------------------------------------------------------------------------------------------
+def _eval_view(t, name, width, n=None):
+    """(tensor, stride in floats) of one float argument of the evaluation kernels; validates everything but the device."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() == 2 and width == 1 and t.shape[1] == 1:
+        t = t[:, 0]
+    if (t.dim() != 1 if width == 1 else (t.dim() != 2 or t.shape[1] != width)):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {('*',) if width == 1 else ('*', width)}")
+    if n is not None and t.shape[0] != n:
+        raise ValueError(f"{name} holds {t.shape[0]} rows, expected {n}")
+    if width > 1 and t.shape[0] > 0 and t.stride(1) != 1:
+        raise ValueError(f"{name} must have unit stride along its rows, got stride {t.stride(1)}")
+    stride = int(t.stride(0))
+    if t.shape[0] <= 1:
+        stride = max(stride, width)
+    if stride < width:
+        raise ValueError(f"{name} has a row stride of {stride} floats, smaller than its width {width}")
+    return t, stride
+
+
+def _eval_classes(n_classes):
+    c = int(n_classes)
+    if not 1 <= c <= _capi.MAX_CLASSES:
+        raise ValueError(f"n_classes={c}: the evaluation kernels take 1 .. {_capi.MAX_CLASSES} classes")
+    return c
+
+
+def _eval_devices(named):
+    """All tensors on one device, and that device a HIP one."""
+    like_name, like = named[0]
+    for name, t in named[1:]:
+        if t.device != like.device:
+            raise ValueError(f"{name} is on {t.device}, expected {like.device} ({like_name}'s device)")
+    if not like.is_cuda:
+        raise RuntimeError(f"{like_name} lives on {like.device}: intrinsicnerf_amd runs only on a HIP device (no CPU / eager fallback exists)")
+    return like.device
+
+
+def sem_maps(logits, label=None, entropy=None, want_label=True, want_entropy=True):
+    """Label map and entropy map of semantic logits [n, C] in one launch of ``inerf_sem_maps`` (trainer.py:1244-1245): the lowest
+    index of each row's maximum as a float, and the entropy of its softmax.  ``label`` / ``entropy``: [n] fp32 views to write into
+    (any element stride: a column of a pack), allocated when not given and wanted.  Returns ``(label, entropy)``."""
+    if isinstance(logits, torch.Tensor) and logits.dim() == 2:
+        width = int(logits.shape[1])
+    else:
+        raise ValueError("logits must be a [n, C] tensor" if isinstance(logits, torch.Tensor) else "logits must be a torch.Tensor")
+    c = _eval_classes(width)
+    logits, ld = _eval_view(logits, "logits", c)
+    n = logits.shape[0]
+    named = [("logits", logits)]
+    outs = []
+    for name, t, want in (("label", label, want_label), ("entropy", entropy, want_entropy)):
+        if t is not None:
+            t, st = _eval_view(t, name, 1, n)
+            named.append((name, t))
+        elif want:
+            t, st = torch.empty(n, dtype=torch.float32, device=logits.device), 1
+        else:
+            st = 1
+        outs.append((t, st))
+    device = _eval_devices(named)
+    (label, lst), (entropy, est) = outs
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_sem_maps(_ptr(logits), ld, n, c, _ptr(label), lst, _ptr(entropy), est, _stream(logits))
+    _capi.check(rc, "inerf_sem_maps")
+    return label, entropy
+
+
+def eval_workspace_bytes(n):
+    return int(_capi.lib().inerf_eval_workspace_bytes(int(n)))
+
+
+def eval_tables(n_classes, device):
+    """Zeroed accumulators of ``eval_accumulate``: ``counts`` [C * C + 8] int64 and ``sums`` [6] float64 on ``device``."""
+    c = _eval_classes(n_classes)
+    return (torch.zeros(c * c + _capi.EVAL_COUNTS, dtype=torch.int64, device=device),
+            torch.zeros(_capi.EVAL_SUMS, dtype=torch.float64, device=device))
+
+
+def eval_accumulate(counts, sums, n_classes, ignore_label=-1, logits=None, pred_label=None, true_label=None, depth_pred=None,
+                    depth_trgt=None, rgb_pred=None, rgb_trgt=None, out_label=None, out_entropy=None, want_maps=True, workspace=None):
+    """One pass of ``inerf_eval_accumulate`` over n pixels, ADDING into ``counts`` / ``sums`` (``eval_tables``; the caller zeroes
+    them): the confusion table of (``true_label``, predicted label) - the prediction a float column ``pred_label`` or derived
+    from ``logits`` [n, C] in the same launch -, the depth counts and error sums of (``depth_trgt``, ``depth_pred``) and the squared
+    error of (``rgb_pred``, ``rgb_trgt``) [n, 3].  Each group is optional.  With ``logits`` the label and entropy maps are written
+    as ``sem_maps`` writes them (``out_label`` / ``out_entropy``, allocated when not given unless ``want_maps`` is false) and
+    returned; otherwise ``(None, None)``."""
+    c = _eval_classes(n_classes)
+    for name, t, size, dtype in (("counts", counts, c * c + _capi.EVAL_COUNTS, torch.int64), ("sums", sums, _capi.EVAL_SUMS, torch.float64)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 1 and t.shape[0] == size and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} vector of {size} entries ({c} classes)")
+    named = [("counts", counts), ("sums", sums)]
+    a = _capi.EvalArgs()
+    a.n_classes, a.ignore_label = c, int(ignore_label)
+    n = None
+    held = []
+
+    def take(name, t, width):
+        nonlocal n
+        t, st = _eval_view(t, name, width, n)
+        n = t.shape[0]
+        named.append((name, t))
+        held.append(t)
+        setattr(a, name, t.data_ptr())
+        setattr(a, name + "_stride", st)
+        return t
+
+    if logits is not None:
+        if pred_label is not None:
+            raise ValueError("pred_label and logits are alternatives: give one")
+        if not (isinstance(logits, torch.Tensor) and logits.dim() == 2 and logits.shape[1] == c):
+            raise ValueError(f"logits must be a [n, {c}] tensor, got {tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+        logits = take("logits", logits, c)
+    if true_label is not None:
+        if logits is None and pred_label is None:
+            raise ValueError("true_label needs a prediction: pred_label or logits")
+        take("true_label", true_label, 1)
+        if pred_label is not None:
+            take("pred_label", pred_label, 1)
+    elif pred_label is not None:
+        raise ValueError("pred_label given without true_label")
+    for (pn, p), (tn, t), width in ((("depth_pred", depth_pred), ("depth_trgt", depth_trgt), 1), (("rgb_pred", rgb_pred), ("rgb_trgt", rgb_trgt), 3)):
+        if (p is None) != (t is None):
+            raise ValueError(f"{pn} and {tn} go together")
+        if p is not None:
+            take(pn, p, width)
+            take(tn, t, width)
+    if n is None:
+        raise ValueError("eval_accumulate: no group given (logits, true_label, depth_pred or rgb_pred)")
+    label = entropy = None
+    if logits is not None:
+        for name, t in (("out_label", out_label), ("out_entropy", out_entropy)):
+            if t is not None:
+                take(name, t, 1)
+            elif want_maps:
+                t = torch.empty(n, dtype=torch.float32, device=logits.device)
+                setattr(a, name, t.data_ptr())
+                setattr(a, name + "_stride", 1)
+            if name == "out_label":
+                label = t
+            else:
+                entropy = t
+    elif out_label is not None or out_entropy is not None:
+        raise ValueError("out_label / out_entropy are written only with logits")
+    if workspace is not None:
+        if not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.float64 and workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous float64 tensor")
+        named.append(("workspace", workspace))
+    device = _eval_devices(named)
+    a.n = n
+    need = eval_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+    a.counts, a.sums = counts.data_ptr(), sums.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_eval_accumulate(C.byref(a), _stream(counts))
+    del held
+    _capi.check(rc, "inerf_eval_accumulate")
+    return label, entropy

@@ -55,6 +55,13 @@ the inverse-CDF variates - inside the kernels (csrc/draws.h, ``draws.DrawState``
 own seeding.  The draws are this package's counter-based ones, not torch's streams: a seeded run is reproducible, and its renders do
 not depend on ``chunk``.  Without the flag nothing of this is bound.
 
+``--inerf-eval`` (opt-in) rebinds the reference's two metric functions - ``calculate_segmentation_metrics`` and
+``calculate_depth_metrics`` - to ``evaluation``'s (csrc/eval.hip: one accumulate launch, finished on the host in float64) in both
+``SSR.training.trainer`` (which holds them by value, trainer.py:15) and ``SSR.training.training_utils``.  That alone lets the
+reference's validation step run on a current numpy: its own function uses ``np.float``, which numpy 1.24 removed.  Wiring an
+``evaluation.FrameEvaluator`` into the unedited trainer is out of scope - which ray set pairs with which targets is the trainer's
+knowledge (INTEGRATION.md has the four lines).  ``run_nerf.py`` has no metric functions: the flag only says so, once.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -200,7 +207,25 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     return names
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False):
+EVAL_SYMBOLS = ("calculate_segmentation_metrics", "calculate_depth_metrics")
+EVAL_MODULES = ("SSR.training.trainer", "SSR.training.training_utils")
+
+
+def rebind_eval():
+    """The two metric functions onto the (already imported) reference modules that hold them: {module name: [names bound]}."""
+    from . import evaluation
+    bound = {}
+    for mod_name in EVAL_MODULES:
+        mod = sys.modules.get(mod_name)
+        if mod is None:
+            continue
+        for name in EVAL_SYMBOLS:
+            setattr(mod, name, getattr(evaluation, name))
+        bound[mod_name] = list(EVAL_SYMBOLS)
+    return bound
+
+
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False, evaluate=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
@@ -246,6 +271,9 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
     if draws:                                          # (without the flag SSRTrainer.draws is the mixin's default, None)
         trainer.SSRTrainer.draws = _TrainerDraws()
         bound["SSR.training.trainer.SSRTrainer"].append("draws")
+    if evaluate:                                       # trainer.py:15 imported training_utils and holds both functions by value
+        for mod_name, names in rebind_eval().items():
+            bound.setdefault(mod_name, []).extend(names)
     return bound
 
 
@@ -261,7 +289,21 @@ def _object_batches_notice():
         _told_object_batches = True
 
 
-def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False):
+_told_object_eval = False
+
+
+def _object_eval_notice():
+    """Said once: run_nerf.py computes no validation metrics beyond its inline PSNR; there is nothing to rebind."""
+    global _told_object_eval
+    if not _told_object_eval:
+        print("intrinsicnerf_amd.launch: --inerf-eval has no effect on run_nerf.py: it has no metric functions "
+              "(calculate_segmentation_metrics / calculate_depth_metrics belong to train_SSR_main.py).  evaluation.image_mse_psnr "
+              "serves a loop of your own (INTEGRATION.md).", file=sys.stderr)
+        _told_object_eval = True
+
+
+def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False,
+            evaluate=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -278,9 +320,12 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
         mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws, cluster_refresh)
         if batches:
             _object_batches_notice()
+        if evaluate:
+            _object_eval_notice()
     else:
         importlib.import_module("SSR.training.trainer")
-        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws, cluster_refresh)
+        extra = dict(evaluate=True) if evaluate else {}           # (only when given: a stand-in rebind_ssr of the older signature keeps working)
+        mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws, cluster_refresh, **extra)
     return mod, main
 
 
@@ -307,6 +352,9 @@ def main(argv=None):
     draws = "--inerf-draws" in argv
     if draws:
         argv.remove("--inerf-draws")
+    evaluate = "--inerf-eval" in argv
+    if evaluate:
+        argv.remove("--inerf-eval")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -321,6 +369,8 @@ def main(argv=None):
         extra["draws"] = True
     if cluster_refresh:
         extra["cluster_refresh"] = True
+    if evaluate:
+        extra["evaluate"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

@@ -309,6 +309,7 @@ class SSRRenderMixin:
     return_raw = True
     check_numerics = True
     cluster_refresh = None        # a refresh.ClusterRefresh: render_path(update_cluster=True) keeps its sample set, fit and c / edit images on the device
+    frame_evaluator = None        # an evaluation.FrameEvaluator: render_path takes the label / entropy maps from csrc/eval.hip and accumulates the metrics of registered frame sets
     # a draws.DrawState: in training mode the jitter, the per-ray u (perturb > 0) and the density noise (raw_noise_std > 0) are drawn inside
     # the kernels as a function of (seed, step, stream, global ray index, sample) - the same bits for any `chunk`; None: torch's generator
     draws = None
@@ -343,7 +344,9 @@ class SSRRenderMixin:
         far`` like the reference.  ``update_cluster`` needs ``self.cluster_manager_factory`` (the reference's
         ``Cluster_Manager``: its mean-shift fitting is training control plane, not rebuilt here) - or ``self.cluster_refresh`` (a
         ``refresh.ClusterRefresh``; opt-in): the sample set, the fit and the ``c*`` / ``edit*`` images then stay on the device
-        (csrc/refresh.hip), with the same returned values and files."""
+        (csrc/refresh.hip), with the same returned values and files.  ``self.frame_evaluator`` (an ``evaluation.FrameEvaluator``;
+        opt-in): the two semantic maps come from one launch of csrc/eval.hip instead of the six torch expressions, and the metrics of
+        a frame set registered with it are accumulated in that launch; the returned tuple and the files keep shapes and dtypes."""
         import os
         import numpy as np
         from . import frames
@@ -399,10 +402,19 @@ class SSRRenderMixin:
         on_device = bool(update_cluster) and refresh is not None
         class_num = (1 if getattr(self, "no_semantic_tree", False) else self.num_valid_semantic_class) if on_device else None
         streamer, in_flight = None, []
+        evaluator = getattr(self, "frame_evaluator", None)
+        if evaluator is not None:
+            evaluator.begin(rays)
         for i in range(len(rays)):
             out = self.render_rays(rays[i])
             maps = {k: out[k].detach() for k in keys if k in out}
-            if self.enable_semantic:
+            if evaluator is not None:
+                # one launch: both maps and, for a registered frame set, the confusion table and the depth / rgb sums
+                label, entropy = evaluator.add_frame(i, logits=out[f"sem_logits_{lvl}"].detach() if self.enable_semantic else None,
+                                                     depth=maps[f"depth_{lvl}"], rgb=maps[f"rgb_{lvl}"])
+                if self.enable_semantic:
+                    maps["sem_label"], maps["sem_entropy"] = label, entropy
+            elif self.enable_semantic:
                 logits = out[f"sem_logits_{lvl}"].detach()
                 logp = F.log_softmax(logits, dim=-1)
                 maps["sem_label"] = torch.argmax(F.softmax(logits, dim=-1), dim=-1).float()         # < 2^24: exact in fp32
