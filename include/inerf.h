@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40020
+#define INERF_ABI_VERSION 40021
 
 /* error codes */
 #define INERF_OK              0
@@ -992,8 +992,10 @@ int inerf_batch_assemble(const inerf_batch_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mesh extraction: the query lattice of a scene's oriented bounding box and the occupancy of a trained network on it
- * (SSR/extract_colour_mesh.py:149-185, SSR/geometry/occupancy.py:5-48).  Marching cubes stays with the caller (skimage, on the
- * returned array); the vertex-colour rays are ordinary inerf_render_rays launches.
+ * (SSR/extract_colour_mesh.py:149-185, SSR/geometry/occupancy.py:5-48), then - after marching cubes and the mesh cleaning, which
+ * stay with the caller (skimage and open3d, on the returned array) - the vertex-colour pass (extract_colour_mesh.py:232-257): one ray
+ * per mesh vertex (inerf_vertex_rays), ordinary inerf_render_rays launches, and the 8-bit colour of every vertex written on the
+ * device (inerf_vertex_colours), so that three bytes per vertex travel to the host.
  * ------------------------------------------------------------------------------------------- */
 #define INERF_MAX_GRID_DIM 1024           /* points per lattice axis: dim^3 <= 2^30 fits the kernels' 32-bit point index */
 
@@ -1032,6 +1034,51 @@ int inerf_occupancy_grid(const inerf_net_desc* net, const float* packed_weights,
                          const float* scale /*[host] 3*/, const float* transform /*[host] 12*/, float dist, int64_t first_point,
                          int64_t n_points, float* occ_out /*[n_points]*/, float* sigma_out /*[n_points] or NULL*/,
                          int32_t* status, int64_t status_points, void* stream);
+
+/* element type of inerf_vertex_rays' input rows */
+#define INERF_DTYPE_F32 0
+#define INERF_DTYPE_F64 1
+
+/* The [n, 11] ray batch of the vertex-colour pass (extract_colour_mesh.py:232-238) in ONE launch: one ray per mesh vertex, cast
+ * against the vertex normal from near * near_t in front of the surface.  Per vertex v with normal m, everything in fp32, every
+ * operation rounded on its own, nothing contracted - the bits of the reference's CPU tensors (tests/golden/vertex_rays.npz):
+ *   d = -m                                                 (:232)   columns 3:6
+ *   o_k = v_k - ((d_k * near) * near_t)                    (:235)   columns 0:3; near and near_t are fp32 numbers (what ATen makes
+ *                                                                   of `near` = 0.1 * ones and of the Python float args.near_t)
+ *   columns 6, 7 = near, far                               (:233-234)
+ *   viewdir = d / |d|                                      (:236-237) columns 8:11; the norm and the true division of
+ *                                                                   inerf_assemble_rays: |d| = sqrt(fma(d2, d2, fma(d1, d1, d0 * d0)))
+ * An all-zero normal gives 0 / 0 = NaN view directions, as the reference does.  It is a source form of inerf_assemble_rays' kernel
+ * body (csrc/frame_ops.hip): the view direction and the column writing are that code.
+ * vertices / normals: rows of three elements of in_dtype, consecutive rows v_stride / n_stride (>= 3) ELEMENTS apart.
+ * INERF_DTYPE_F64 (open3d hands out float64 arrays; the reference rounds them with torch.FloatTensor(...), :232, :235): every
+ * element is rounded to the nearest fp32 first, inside the kernel.  rays_out must not overlap the inputs.
+ * n == 0 is a no-op, whatever the other arguments.  INERF_E_INVALID: an in_dtype that is neither constant, a null pointer, n < 0, a
+ * stride < 3, a pointer not aligned to its element size; INERF_E_UNSUPPORTED beyond (2^31 - 1) * 256 vertices. */
+int inerf_vertex_rays(const void* vertices, int64_t v_stride, const void* normals, int64_t n_stride, int64_t n, int in_dtype,
+                      float near, float far, float near_t, float* rays_out /*[n,11]*/, void* stream);
+
+/* The same function of the same arguments on HOST pointers, evaluated by the calling thread from the same source
+ * (inerf_grid_points_host is its model): the bits can be pinned, and CPU tensors served (geometry.vertex_rays), without a device. */
+int inerf_vertex_rays_host(const void* vertices /*[host]*/, int64_t v_stride, const void* normals /*[host]*/, int64_t n_stride,
+                           int64_t n, int in_dtype, float near, float far, float near_t, float* rays_out /*[host] [n,11]*/);
+
+/* The 8-bit colour of n mesh vertices from what inerf_render_rays returned for their rays, in ONE launch
+ * (extract_colour_mesh.py:248-257).  Exactly one of rgb and logits is non-NULL (both or neither: INERF_E_INVALID):
+ *   colour mode (rgb: rows of three floats, rgb_stride >= 3 floats apart): colours_out = to8b(rgb) (:253-255) =
+ *     (uint8)(255 * clip(x, 0, 1)), NaN -> 0: byte-equal to inerf_frame_to_u8.  n_classes and colour_map are not read.
+ *   semantic mode (logits: rows of n_classes floats, logits_stride >= n_classes floats apart - a column range of a wider row
+ *     goes in as it is): label = the label of inerf_sem_maps - its device function, so the lowest index of the row's maximum
+ *     logit, and 0 for a row that holds a NaN or whose maximum is not finite - and colours_out = colour_map[label] (:249-251).
+ *     colour_map: [n_classes, 3] bytes on the DEVICE (the caller's valid_colour_map).  1 <= n_classes <= INERF_MAX_CLASSES, else
+ *     INERF_E_UNSUPPORTED.  labels_out: the labels as int32, or NULL (either mode; not written in colour mode).
+ * colours_out: [n, 3] bytes, contiguous.  n == 0 is a no-op once the mode, the strides and n_classes have passed.
+ * INERF_E_INVALID: n < 0, a stride smaller than its row, a null colours_out (or colour_map in semantic mode), a float or int32
+ * pointer that is not 4-byte aligned; INERF_E_UNSUPPORTED: more than 2^31 - 1 blocks of 256 vertices.  Nothing is allocated,
+ * synchronised or read on the host. */
+int inerf_vertex_colours(const float* rgb, int64_t rgb_stride, const float* logits, int64_t logits_stride, int64_t n, int n_classes,
+                         const unsigned char* colour_map /*[n_classes,3]*/, unsigned char* colours_out /*[n,3]*/,
+                         int32_t* labels_out /*[n] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Validation metrics (csrc/eval.hip): the label and entropy maps of a rendered frame (SSR/training/trainer.py:1244-1245) and the

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40020          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40021          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -25,6 +25,7 @@ BASE_CHANNELS, ENDPOINT_DIM, RAY_FLOATS, MAX_CLASSES = 11, 128, 11, 240
 # size limits of the per-ray stage kernels (INERF_MAX_SAMPLES ... of include/inerf.h): E_UNSUPPORTED beyond them
 MAX_SAMPLES, MIN_COARSE, MAX_COARSE, MIN_BINS, MAX_IMPORTANCE = 1024, 3, 256, 2, 512
 MAX_GRID_DIM = 1024           # INERF_MAX_GRID_DIM: points per axis of the mesh-extraction lattice
+DTYPE_F32, DTYPE_F64 = 0, 1   # INERF_DTYPE_*: element type of inerf_vertex_rays' vertex and normal rows
 
 _ERR = {E_INVALID: "invalid argument", E_UNSUPPORTED: "unsupported configuration",
         E_WORKSPACE: "workspace missing or too small", E_HIP: "HIP runtime error"}
@@ -236,6 +237,9 @@ SYMBOLS = {
     "inerf_grid_points": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _L, _L, _P, _P]),
     "inerf_grid_points_host": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _L, _L, _P]),
     "inerf_occupancy_grid": (_I, [C.POINTER(NetDesc), _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _L, _L, _P, _P, _P, _L, _P]),
+    "inerf_vertex_rays": (_I, [_P, _L, _P, _L, _L, _I, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "inerf_vertex_rays_host": (_I, [_P, _L, _P, _L, _L, _I, C.c_float, C.c_float, C.c_float, _P]),
+    "inerf_vertex_colours": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P]),
     "inerf_sem_maps": (_I, [_P, _L, _L, _I, _P, _L, _P, _L, _P]),
     "inerf_eval_workspace_bytes": (_L, [_L]),
     "inerf_eval_accumulate": (_I, [C.POINTER(EvalArgs), _P]),

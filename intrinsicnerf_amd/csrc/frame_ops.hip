@@ -1,8 +1,9 @@
 // frame_ops.hip - image-level producers / consumers either side of render_rays:
 //   k_ray_forms    : every ray batch the object-level and SSR front-ends hand to the renderer, one body over
-//                    {source: pinhole pose | given rays} x {NDC off | on} x {output: [N, 11] batch | (o, d) alone}
+//                    {source: pinhole pose | given rays | mesh vertex + normal} x {NDC off | on} x {output: [N, 11] batch | (o, d) alone}
 //                      pose  -> [N, 11]   run_nerf_helpers.py:359-368 + run_nerf.py:99-128 | rays.py:27-67, 223-256
 //                      (o,d) -> [N, 11]   run_nerf.py:106-128 (render(rays=...): every object-level training step)
+//                      (v,n) -> [N, 11]   SSR/extract_colour_mesh.py:232-238 (one ray per mesh vertex, against its normal)
 //                      NDC                run_nerf_helpers.py:381-399 (run_nerf.py:117-119: the LLFF configs)
 //   k_frame_to_u8  : to8b of rendered maps on the device (run_nerf_helpers.py:13 | trainer.py:1242), so that an image
 //                    loop (run_nerf.py:142-212 | trainer.py:1221-1389) moves a quarter of the bytes to the host
@@ -26,14 +27,37 @@
 //   O    = ((sx o'_x) / o'_z, (sy o'_y) / o'_z, 1 + rz c2)       a correctly rounded reciprocal, THEN the product
 //   D    = (sx (d_x / d_z - o'_x / o'_z), sy (d_y / d_z - o'_y / o'_z), rz cm2)   every quotient its own true division
 // View directions are the world-space direction over its norm, taken before NDC.
-// Built with -ffp-contract=off; every operation below is an explicit __f*_rn.
+// Vertex rays (extract_colour_mesh.py:232-238), with near and near_t as fp32 scalars - what ATen makes of a Python number next to a
+// float tensor - and float64 vertices / normals rounded to nearest fp32 first (torch.FloatTensor(np.asarray(...)), :232, :235):
+//   d = -n;   o_k = v_k - ((d_k near) near_t)            two products, each rounded, then the subtraction - no fma
+//   columns 6, 7 = near, far;   view direction = d / |d| as above
+// Built with -ffp-contract=off; every operation below is an explicit __f*_rn.  The vertex form and the eleven columns are also
+// evaluated on the host (inerf_vertex_rays_host): rn_* below are the intrinsic on the device and the plain operator, fmaf and sqrtf
+// (each correctly rounded, nothing contracted) on the host.
 #include <hip/hip_runtime.h>
+
+#include <math.h>
 
 #include "layout.h"
 
 namespace inerf {
 
 int record(hipError_t e);
+
+#define INERF_HD __host__ __device__ __forceinline__
+#if defined(__HIP_DEVICE_COMPILE__)
+INERF_HD float rn_mul(float a, float b) { return __fmul_rn(a, b); }
+INERF_HD float rn_sub(float a, float b) { return __fsub_rn(a, b); }
+INERF_HD float rn_div(float a, float b) { return __fdiv_rn(a, b); }
+INERF_HD float rn_fma(float a, float b, float c) { return __fmaf_rn(a, b, c); }
+#else
+INERF_HD float rn_mul(float a, float b) { return a * b; }
+INERF_HD float rn_sub(float a, float b) { return a - b; }
+INERF_HD float rn_div(float a, float b) { return a / b; }
+INERF_HD float rn_fma(float a, float b, float c) { return fmaf(a, b, c); }
+#endif
+
+enum { kSrcPose = 0, kSrcGiven = 1, kSrcVertex = 2 };
 
 struct RayFormParams {
     const float* poses;        // [B] camera-to-world matrices, rows of 4 floats, `pose_stride` floats apart
@@ -49,6 +73,11 @@ struct RayFormParams {
     float fx, fy, cx, cy, near, far;
     int opengl;                // 1: dirs = (x, -y, -1) (object-level, SSR convention "opengl"); 0: (x, y, 1) ("opencv")
     float sx, sy, nr, c2, cm2; // NDC coefficients (see the header comment)
+    const void* vertices;      // vertex form: rows of 3 floats (in_f64: doubles), `v_stride` / `n_stride` ELEMENTS apart
+    const void* normals;
+    long long v_stride, n_stride;
+    int in_f64;
+    float near_t;
 };
 
 __device__ __forceinline__ void rotate(const float* __restrict__ p, float x, float y, float z, float (&d)[3]) {
@@ -73,20 +102,50 @@ __device__ __forceinline__ void ndc_project(const RayFormParams& p, float (&o)[3
     d[2] = __fmul_rn(rz, p.cm2);
 }
 
-// GIVEN: rays from rays_o / rays_d instead of a pose; NDC: ndc_project on origin and direction; SPLIT: write (o, d) as two
-// [N, 3] tensors instead of the [N, 11] batch (no view direction, no near / far)
-template <bool GIVEN, bool NDC, bool SPLIT>
+// extract_colour_mesh.py:232-235: the ray of one mesh vertex, cast against its normal from near * near_t in front of the surface
+template <typename T>
+INERF_HD void vertex_ray(const T* __restrict__ vtx, const T* __restrict__ nrm, float near, float near_t, float (&o)[3], float (&d)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float x = (float)vtx[k], n = (float)nrm[k];              // float64: round to nearest fp32, once
+        d[k] = -n;
+        o[k] = rn_sub(x, rn_mul(rn_mul(d[k], near), near_t));
+    }
+}
+
+// the eleven floats of one ray: [o3, d3, near, far, v / |v|]
+INERF_HD void ray_columns(const float (&o)[3], const float (&d)[3], const float (&v)[3], float near, float far, float* __restrict__ s) {
+    // sqrtf, not __fsqrt_rn: the latter lowers to a bare v_sqrt_f32 (1 ulp); ocml's sqrtf carries the correctly-rounding fix-up
+    const float nrm = sqrtf(rn_fma(v[2], v[2], rn_fma(v[1], v[1], rn_mul(v[0], v[0]))));
+    s[0] = o[0]; s[1] = o[1]; s[2] = o[2];
+    s[3] = d[0]; s[4] = d[1]; s[5] = d[2];
+    s[6] = near; s[7] = far;
+    s[8] = rn_div(v[0], nrm); s[9] = rn_div(v[1], nrm); s[10] = rn_div(v[2], nrm);
+}
+
+// SRC: rays from a pose, from rays_o / rays_d, or from a mesh vertex and its normal; NDC: ndc_project on origin and direction;
+// SPLIT: write (o, d) as two [N, 3] tensors instead of the [N, 11] batch (no view direction, no near / far)
+template <int SRC, bool NDC, bool SPLIT>
 __global__ __launch_bounds__(256) void k_ray_forms(const RayFormParams p) {
     __shared__ float stage[256 * (SPLIT ? 6 : INERF_RAY_FLOATS)];
     const long long base = (long long)blockIdx.x * 256;
     const long long idx = base + threadIdx.x;
     if (idx < p.n_rays) {
         float o[3], d[3], v[3];
-        if constexpr (GIVEN) {
+        if constexpr (SRC == kSrcGiven) {
             const float* __restrict__ ro = p.rays_o + idx * p.o_stride;
             const float* __restrict__ rd = p.rays_d + idx * p.d_stride;
 #pragma unroll
             for (int k = 0; k < 3; ++k) { o[k] = ro[k]; d[k] = rd[k]; v[k] = d[k]; }
+        } else if constexpr (SRC == kSrcVertex) {
+            if (p.in_f64)
+                vertex_ray(static_cast<const double*>(p.vertices) + idx * p.v_stride, static_cast<const double*>(p.normals) + idx * p.n_stride,
+                           p.near, p.near_t, o, d);
+            else
+                vertex_ray(static_cast<const float*>(p.vertices) + idx * p.v_stride, static_cast<const float*>(p.normals) + idx * p.n_stride,
+                           p.near, p.near_t, o, d);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = d[k];
         } else {
             const long long hw = (long long)p.H * p.W;
             const int b = (int)(idx / hw);
@@ -113,13 +172,7 @@ __global__ __launch_bounds__(256) void k_ray_forms(const RayFormParams p) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) { stage[threadIdx.x * 3 + k] = o[k]; stage[768 + threadIdx.x * 3 + k] = d[k]; }
         } else {
-            // sqrtf, not __fsqrt_rn: the latter lowers to a bare v_sqrt_f32 (1 ulp); ocml's sqrtf carries the correctly-rounding fix-up
-            const float nrm = sqrtf(__fmaf_rn(v[2], v[2], __fmaf_rn(v[1], v[1], __fmul_rn(v[0], v[0]))));
-            float* s = stage + threadIdx.x * INERF_RAY_FLOATS;
-            s[0] = o[0]; s[1] = o[1]; s[2] = o[2];
-            s[3] = d[0]; s[4] = d[1]; s[5] = d[2];
-            s[6] = p.near; s[7] = p.far;
-            s[8] = __fdiv_rn(v[0], nrm); s[9] = __fdiv_rn(v[1], nrm); s[10] = __fdiv_rn(v[2], nrm);
+            ray_columns(o, d, v, p.near, p.far, stage + threadIdx.x * INERF_RAY_FLOATS);
         }
     }
     __syncthreads();
@@ -176,8 +229,8 @@ extern "C" int inerf_gen_rays_ndc(const float* poses, int pose_stride, const flo
     set_ndc(p, ndc);
     const long long blocks = (p.n_rays + 255) / 256;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    if (ndc) hipLaunchKernelGGL((k_ray_forms<false, true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_ray_forms<false, false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    if (ndc) hipLaunchKernelGGL((k_ray_forms<kSrcPose, true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((k_ray_forms<kSrcPose, false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     return record(hipGetLastError());
 }
 
@@ -198,8 +251,8 @@ extern "C" int inerf_assemble_rays(const float* rays_o, int64_t o_stride, const 
     set_ndc(p, ndc);
     const long long blocks = (p.n_rays + 255) / 256;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    if (ndc) hipLaunchKernelGGL((k_ray_forms<true, true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_ray_forms<true, false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    if (ndc) hipLaunchKernelGGL((k_ray_forms<kSrcGiven, true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((k_ray_forms<kSrcGiven, false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     return record(hipGetLastError());
 }
 
@@ -213,8 +266,53 @@ extern "C" int inerf_ndc_rays(const float* rays_o, int64_t o_stride, const float
     set_ndc(p, ndc);
     const long long blocks = (p.n_rays + 255) / 256;
     if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
-    hipLaunchKernelGGL((k_ray_forms<true, true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((k_ray_forms<kSrcGiven, true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     return record(hipGetLastError());
+}
+
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// INERF_OK when the rows are ones both forms of inerf_vertex_rays take (n > 0)
+static int vertex_args(const void* vertices, int64_t v_stride, const void* normals, int64_t n_stride, int64_t n, int in_dtype,
+                       const float* rays_out) {
+    if (in_dtype != INERF_DTYPE_F32 && in_dtype != INERF_DTYPE_F64) return INERF_E_INVALID;
+    if (!vertices || !normals || !rays_out || n < 0 || v_stride < 3 || n_stride < 3) return INERF_E_INVALID;
+    const uintptr_t a = in_dtype == INERF_DTYPE_F64 ? 8 : 4;
+    if (misaligned(vertices, a) || misaligned(normals, a) || misaligned(rays_out, 4)) return INERF_E_INVALID;
+    return INERF_OK;
+}
+
+extern "C" int inerf_vertex_rays(const void* vertices, int64_t v_stride, const void* normals, int64_t n_stride, int64_t n, int in_dtype,
+                                 float near, float far, float near_t, float* rays_out, void* stream) {
+    using namespace inerf;
+    if (n == 0) return INERF_OK;
+    const int rc = vertex_args(vertices, v_stride, normals, n_stride, n, in_dtype, rays_out);
+    if (rc != INERF_OK) return rc;
+    RayFormParams p = {};
+    p.vertices = vertices; p.normals = normals; p.v_stride = v_stride; p.n_stride = n_stride;
+    p.in_f64 = in_dtype == INERF_DTYPE_F64; p.near_t = near_t;
+    p.n_rays = n; p.out = rays_out; p.near = near; p.far = far;
+    const long long blocks = (p.n_rays + 255) / 256;
+    if (blocks > 0x7fffffffLL) return INERF_E_UNSUPPORTED;
+    hipLaunchKernelGGL((k_ray_forms<kSrcVertex, false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return record(hipGetLastError());
+}
+
+extern "C" int inerf_vertex_rays_host(const void* vertices, int64_t v_stride, const void* normals, int64_t n_stride, int64_t n,
+                                      int in_dtype, float near, float far, float near_t, float* rays_out) {
+    using namespace inerf;
+    if (n == 0) return INERF_OK;
+    const int rc = vertex_args(vertices, v_stride, normals, n_stride, n, in_dtype, rays_out);
+    if (rc != INERF_OK) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        float o[3], d[3];
+        if (in_dtype == INERF_DTYPE_F64)
+            vertex_ray(static_cast<const double*>(vertices) + i * v_stride, static_cast<const double*>(normals) + i * n_stride, near, near_t, o, d);
+        else
+            vertex_ray(static_cast<const float*>(vertices) + i * v_stride, static_cast<const float*>(normals) + i * n_stride, near, near_t, o, d);
+        ray_columns(o, d, d, near, far, rays_out + i * INERF_RAY_FLOATS);
+    }
+    return INERF_OK;
 }
 
 extern "C" int inerf_frame_to_u8(const float* values, int64_t n, unsigned char* out, void* stream) {

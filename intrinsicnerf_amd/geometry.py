@@ -4,8 +4,12 @@ Mirrors, with the reference's names, arguments and returned tensors (citations r
   grid_within_bound, make_3D_grid      geometry/occupancy.py:5-48
   occupancy_grid                       extract_colour_mesh.py:149-185 (lattice, chunk loop over run_network, raw[..., 3],
                                        occupancy_activation) - one launch of ``inerf_occupancy_grid`` on the fused networks
-Marching cubes stays with the caller (``skimage.measure.marching_cubes`` on the returned array); the vertex-colour rays are
-``SSRTrainer.render_rays``.  See INTEGRATION.md.
+  vertex_rays                          extract_colour_mesh.py:232-238 (one ray per mesh vertex, against its normal) - one launch of
+                                       ``inerf_vertex_rays``
+  vertex_colours                       extract_colour_mesh.py:27-41, 232-257 (the rays, the chunk loop over render_rays, to8b or
+                                       valid_colour_map[label]) - three bytes per vertex reach the host, once
+Marching cubes and the mesh cleaning stay with the caller (``skimage.measure.marching_cubes`` on the returned array, ``open3d``).  See
+INTEGRATION.md.
 """
 import numpy as np
 import torch
@@ -13,9 +17,10 @@ import torch
 from . import _capi, kernels, layered, packing
 from .object_level import Embedder
 
-__all__ = ["grid_within_bound", "make_3D_grid", "occupancy_grid", "occupancy_activation"]
+__all__ = ["grid_within_bound", "make_3D_grid", "occupancy_grid", "occupancy_activation", "vertex_rays", "vertex_colours"]
 
 STATUS_POINTS = 1 << 20        # lattice points per f16 range word of the fused launch - and per launch of the other paths
+VERTEX_CHUNK = 1 << 16         # vertices per render_rays call of vertex_colours
 
 
 def _rows34(transform):
@@ -165,3 +170,85 @@ def occupancy_grid(net, embed_fn, occ_range, extents, transform, grid_dim, dista
                 exact(first, min(step, total - first))
         occ = occ.reshape(dim, dim, dim)
         return (occ, sigma.reshape(dim, dim, dim)) if return_sigma else occ
+
+
+def _vertex_pair(vertices, normals):
+    """``vertices`` and ``normals`` (numpy or torch, float32 or float64) as two [V, 3] tensors of one dtype, where they are, uncopied
+    unless their dtypes differ (float64 then: its rounding to fp32 is the reference's)."""
+    out = []
+    for name, a in (("vertices", vertices), ("normals", normals)):
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [V, 3]")
+        out.append(t)
+    v, m = out
+    if v.shape != m.shape:
+        raise ValueError(f"vertices {tuple(v.shape)} and normals {tuple(m.shape)} do not match: one normal per vertex")
+    if v.dtype != m.dtype:
+        v, m = v.double(), m.double()
+    return v, m
+
+
+def vertex_rays(vertices, normals, near=0.1, far=10.0, near_t=2.0, device=None):
+    """``[V, 11]`` ray batch of extract_colour_mesh.py:232-238 - ``rays_d = -normals``, ``rays_o = vertices - rays_d * near * near_t``,
+    ``viewdirs = rays_d / |rays_d|``, ``cat([rays_o, rays_d, near, far, viewdirs])`` - with the reference's CPU bits.  ``vertices`` /
+    ``normals``: [V, 3], numpy or torch, float32 or float64 (``np.asarray(mesh.vertices)`` goes in as it is; float64 is rounded to fp32
+    inside, as ``torch.FloatTensor`` does).  ``device`` None: where the inputs live - ``inerf_vertex_rays_host`` on the CPU; a device:
+    the arrays are uploaded as they are and ``inerf_vertex_rays`` runs there, one launch."""
+    v, m = _vertex_pair(vertices, normals)
+    if device is not None:
+        v, m = v.to(device), m.to(device)
+    elif v.device != m.device:
+        raise ValueError(f"vertices are on {v.device} and normals on {m.device}")
+    return kernels.vertex_rays(v, m, near, far, near_t)
+
+
+def _colour_map(colour_map):
+    """the caller's valid_colour_map as a uint8 [C, 3] CPU tensor (extract_colour_mesh.py:250, 257: indexed, then .astype(np.uint8))"""
+    t = colour_map.detach().cpu() if isinstance(colour_map, torch.Tensor) else torch.as_tensor(np.asarray(colour_map))
+    if t.dim() != 2 or t.shape[1] != 3 or not 1 <= t.shape[0] <= _capi.MAX_CLASSES:
+        raise ValueError(f"colour_map has shape {tuple(t.shape)}, expected [C, 3] with 1 <= C <= {_capi.MAX_CLASSES}")
+    return t.to(torch.uint8).contiguous()
+
+
+def vertex_colours(render_rays, vertices, normals, *, near=0.1, far=10.0, near_t=2.0, sem=False, colour_map=None, chunk=None,
+                   return_labels=False):
+    """``uint8 [V, 3]`` vertex colours of extract_colour_mesh.py:232-257 as a numpy array (with ``return_labels``: ``(colours, int32 [V]
+    labels)``): ``to8b(rgb_fine)`` of the ray cast against every vertex normal or, with ``sem``, ``colour_map[label]`` of
+    ``sem_logits_fine`` (``colour_map``: the caller's ``valid_colour_map`` [C, 3], numpy or tensor; the label is ``kernels.sem_maps``').
+
+    ``render_rays``: ``rays [n, 11] -> dict`` (``SSRTrainer.render_rays`` with ``return_raw = False``: SSRRenderMixin.vertex_colours sets
+    that).  ``chunk`` vertices (default 65 536) at a time: their rays are built on the device (``inerf_vertex_rays``), rendered, and the one
+    key that is needed - ``rgb_fine`` / ``sem_logits_fine``, the ``_coarse`` keys of a render without a fine pass - goes through
+    ``inerf_vertex_colours`` into a device ``uint8 [V, 3]``.  Nothing is read back per chunk and no [V, ...] float tensor exists; one copy
+    to the host at the end.  Rays are independent, so the bytes do not depend on ``chunk``."""
+    v, m = _vertex_pair(vertices, normals)
+    if sem and colour_map is None:
+        raise ValueError("sem=True needs colour_map (the [C, 3] valid_colour_map of the scene)")
+    if return_labels and not sem:
+        raise ValueError("return_labels needs sem=True")
+    cmap = _colour_map(colour_map) if sem else None
+    chunk = VERTEX_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk = {chunk}: expected a positive number of vertices")
+    total = v.shape[0]
+    with torch.no_grad():
+        device = v.device if v.is_cuda else (m.device if m.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        colours = torch.empty(total, 3, dtype=torch.uint8, device=device)
+        labels = torch.empty(total, dtype=torch.int32, device=device) if return_labels else None
+        cmap = None if cmap is None else cmap.to(device)
+        what = "sem_logits" if sem else "rgb"
+        for first in range(0, total, chunk):
+            count = min(chunk, total - first)
+            rays = kernels.vertex_rays(v[first:first + count].to(device), m[first:first + count].to(device), near, far, near_t)
+            ret = render_rays(rays)
+            x = ret.get(what + "_fine", ret.get(what + "_coarse"))
+            if x is None:
+                raise KeyError(f"render_rays returned neither {what}_fine nor {what}_coarse")
+            x = x.reshape(count, -1)
+            kernels.vertex_colours(rgb=None if sem else x, logits=x if sem else None, colour_map=cmap, out=colours[first:first + count],
+                                   labels=None if labels is None else labels[first:first + count])
+        colours = colours.cpu().numpy()
+        return (colours, labels.cpu().numpy()) if return_labels else colours

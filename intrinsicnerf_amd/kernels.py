@@ -288,6 +288,87 @@ def occupancy_grid(desc, packed, t, scale, transform, dist, first=0, count=None,
     return occ, sigma
 
 
+def _vertex_rows(t, name):
+    """``t`` [n, 3] float32 or float64, on any device, as (tensor, row stride in elements) without a copy."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [n, 3]")
+    if t.shape[0] > 0 and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 3)):
+        raise ValueError(f"{name} (strides {tuple(t.stride())}) must have unit stride along its rows and a row stride >= 3: pass it .contiguous()")
+    return t, max(int(t.stride(0)), 3)
+
+
+def vertex_rays(vertices, normals, near=0.1, far=10.0, near_t=2.0):
+    """[n, 11] ray batch ``[o3, d3, near, far, viewdir3]`` of the vertex-colour pass (SSR/extract_colour_mesh.py:232-238): ``d = -normal``,
+    ``o = vertex - d * near * near_t``, view direction ``d / |d|``, with the reference's CPU bits, where the inputs live:
+    ``inerf_vertex_rays`` (one launch) for device tensors, ``inerf_vertex_rays_host`` for CPU ones.  ``vertices`` / ``normals``: [n, 3]
+    of one dtype, float32 or float64 (rounded to fp32 inside, as ``torch.FloatTensor(...)`` does), rows any stride >= 3 apart."""
+    v, v_stride = _vertex_rows(vertices, "vertices")
+    m, m_stride = _vertex_rows(normals, "normals")
+    if v.shape != m.shape or v.dtype != m.dtype or v.device != m.device:
+        raise ValueError(f"vertices {tuple(v.shape)} {v.dtype} on {v.device} and normals {tuple(m.shape)} {m.dtype} on {m.device} do not match")
+    n = v.shape[0]
+    dtype = _capi.DTYPE_F64 if v.dtype == torch.float64 else _capi.DTYPE_F32
+    out = torch.empty(n, RAY_FLOATS, dtype=torch.float32, device=v.device)
+    if v.is_cuda:
+        with torch.cuda.device(v.device):
+            rc = _capi.lib().inerf_vertex_rays(_ptr(v), v_stride, _ptr(m), m_stride, n, dtype, float(near), float(far), float(near_t),
+                                               _ptr(out), _stream(v))
+        _capi.check(rc, "inerf_vertex_rays")
+    else:
+        _capi.check(_capi.lib().inerf_vertex_rays_host(_ptr(v), v_stride, _ptr(m), m_stride, n, dtype, float(near), float(far),
+                                                       float(near_t), _ptr(out)), "inerf_vertex_rays_host")
+    return out
+
+
+def vertex_colours(rgb=None, logits=None, colour_map=None, out=None, labels=None):
+    """8-bit vertex colours in one launch of ``inerf_vertex_colours`` (extract_colour_mesh.py:248-257).  Exactly one of ``rgb`` [n, 3]
+    and ``logits`` [n, C] (float32 device views: unit stride along a row, any row stride - a column range of a wider tensor goes in as
+    it is): ``to8b(rgb)`` as ``frame_to_u8`` gives it, or ``colour_map[label]`` with the label of ``sem_maps`` and ``colour_map`` a
+    contiguous uint8 [C, 3] device tensor.  ``out``: contiguous uint8 [n, 3] to write into (rows of a larger buffer), allocated when
+    None.  ``labels``: contiguous int32 [n] to receive the labels, ``True`` to allocate it, None for none (semantic mode only).
+    Returns ``(out, labels)``."""
+    if (rgb is None) == (logits is None):
+        raise ValueError("vertex_colours takes exactly one of rgb and logits")
+    if rgb is not None:
+        if labels is not None:
+            raise ValueError("labels exist only in semantic mode (logits)")
+        src, stride = _eval_view(rgb, "rgb", 3)
+        c, named = 0, [("rgb", src)]
+    else:
+        if (not isinstance(colour_map, torch.Tensor) or colour_map.dtype != torch.uint8 or colour_map.dim() != 2 or colour_map.shape[1] != 3
+                or not colour_map.is_contiguous()):
+            raise ValueError("colour_map must be a contiguous uint8 [C, 3] tensor")
+        c = _eval_classes(colour_map.shape[0])
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != c:
+            raise ValueError(f"logits must be a [n, {c}] tensor, one column per row of colour_map")
+        src, stride = _eval_view(logits, "logits", c)
+        named = [("logits", src), ("colour_map", colour_map)]
+    n = src.shape[0]
+    if out is None:
+        out = torch.empty(n, 3, dtype=torch.uint8, device=src.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 [{n}, 3] tensor")
+    named.append(("out", out))
+    if labels is True:
+        labels = torch.empty(n, dtype=torch.int32, device=src.device)
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+            raise ValueError(f"labels must be a contiguous int32 [{n}] tensor")
+        named.append(("labels", labels))
+    device = _eval_devices(named)
+    u8 = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_vertex_colours(_ptr(src) if rgb is not None else None, stride if rgb is not None else 0,
+                                              _ptr(src) if rgb is None else None, stride if rgb is None else 0, n, c,
+                                              u8(colour_map) if rgb is None else None, u8(out), u8(labels), _stream(src))
+    _capi.check(rc, "inerf_vertex_colours")
+    return out, labels
+
+
 def frame_to_u8(values):
     """``(255 * clip(x, 0, 1)).astype(uint8)`` (to8b, run_nerf_helpers.py:13) on the device; same shape, dtype uint8."""
     values = _dev(values, "values")

@@ -480,6 +480,25 @@ class SSRRenderMixin:
         return geometry.occupancy_grid(self.ssr_net_fine, self.embed_fn, occ_range, extents, transform, grid_dim,
                                        (self.far - self.near) / self.N_importance, embeddirs_fn=self.embeddirs_fn)
 
+    def vertex_colours(self, vertices, normals, near_t=2.0, sem=False, colour_map=None, chunk=None):
+        """``uint8 [V, 3]`` (numpy) colours of the mesh vertices - extract_colour_mesh.py:232-257: one ray per vertex against its normal
+        (near 0.1, far 10.0 as :233-234 hard-code them, ``near_t`` = args.near_t), rendered in eval mode, then ``to8b(rgb_fine)`` or, with
+        ``sem``, ``colour_map[label]`` (default: ``self.valid_colour_map``).  geometry.vertex_colours on ``self.render_rays`` with
+        ``return_raw`` and ``check_numerics`` off for the pass: rays, render and colours stay on the device, three bytes per vertex
+        are copied to the host, once.  The trainer must be in eval mode (the reference sets ``training = False`` first, :129)."""
+        from . import geometry
+        if bool(self.training):
+            raise RuntimeError("vertex_colours renders in eval mode: set training = False first (extract_colour_mesh.py:129)")
+        if colour_map is None:
+            colour_map = getattr(self, "valid_colour_map", None)
+        saved = self.return_raw, self.check_numerics
+        self.return_raw = self.check_numerics = False
+        try:
+            return geometry.vertex_colours(self.render_rays, vertices, normals, near=0.1, far=10.0, near_t=near_t, sem=sem,
+                                           colour_map=colour_map if sem else None, chunk=chunk)
+        finally:
+            self.return_raw, self.check_numerics = saved
+
     def _coalesced(self, flat_rays):
         """``self.chunk``, or the larger number of rays per ``volumetric_rendering`` call that gives the same frame
         (kernels.coalesced_chunk; results are bit-identical for any chunking): only when no random number is drawn per chunk (eval
