@@ -234,7 +234,7 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
     methods = SSR_METHODS + (("render_path",) if with_render_path else ())
     for name in methods:
         setattr(trainer.SSRTrainer, name, getattr(ssr.SSRRenderMixin, name))
-    for extra in ("return_raw", "check_numerics", "_staged", "draws"):          # what the mixin's methods read besides the trainer's attributes
+    for extra in ("return_raw", "check_numerics", "draws"):          # what the mixin's methods read besides the trainer's attributes
         setattr(trainer.SSRTrainer, extra, getattr(ssr.SSRRenderMixin, extra))
     if with_render_path and hasattr(trainer, "Cluster_Manager"):
         # trainer.py:1065 renders with update_cluster = not self.no_cluster: the fitting is the reference's class (trainer.py:16, :1416-1418)

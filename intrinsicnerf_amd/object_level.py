@@ -3,7 +3,9 @@
 Same function names, argument meaning, return structure and error behaviour as the reference, so
 that ``run_nerf.py`` keeps working when it imports these instead of its own definitions
 (INTEGRATION.md).  The arithmetic is done by ``libinerf.so`` (hand-written HIP for gfx950); this
-file is plumbing: shape handling, RNG draws in the reference's order, chunk loops, dict assembly.
+file is plumbing: shape handling, RNG draws in the reference's order, dict assembly.  The control
+path it shares with ``ssr.py`` - fusability, the chunk loop with its f16 range fallback, the staged
+pass of a training step - is ``render_core.py``.
 
 Reference lines (relative to ``/root/reference/object_level``):
   render          run_nerf.py:74-139        batchify_rays   run_nerf.py:59-71
@@ -17,7 +19,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _capi, kernels, layered, packing
+from . import _capi, kernels, render_core
+from .render_core import (FP32_LAYERS_NOTE, _fusable, _layered_spec, _run_network_torch, _train_desc, _train_query,  # noqa: F401
+                          _training_path_notice, _unfused_notice, _wants_grad)       # (they live in render_core.py; importable from here as before)
 from .losses import compute_intrinsic_loss, object_step_loss  # noqa: F401  (run_nerf_helpers.py:59-86, run_nerf.py:976-1013 on csrc/losses.hip)
 
 __all__ = ["Embedder", "get_embedder", "NeRF", "NetworkQuery", "run_network", "raw2outputs", "sample_pdf",
@@ -162,92 +166,6 @@ def _as_network_query(q):
     return NetworkQuery(embed_fn, embeddirs_fn)
 
 
-def _fusable(network_fn, embed_fn, embeddirs_fn):
-    """Descriptor if (network, encoders) is a combination the fused kernel implements, else None."""
-    if not hasattr(network_fn, "fused_desc"):
-        return None
-    desc = network_fn.fused_desc()
-    if desc is None or not isinstance(embed_fn, Embedder) or not isinstance(embeddirs_fn, Embedder):
-        return None
-    if embed_fn.n_freqs != desc.l_xyz or embeddirs_fn.n_freqs != desc.l_dir or embeddirs_fn.scalar_factor != 1.0:
-        return None
-    desc.xyz_div = embed_fn.scalar_factor
-    return desc
-
-
-def _wants_grad(*modules):
-    """True inside a training step: autograd is recording and some network parameter is trainable."""
-    return torch.is_grad_enabled() and any(p.requires_grad for m in modules if isinstance(m, nn.Module) for p in m.parameters())
-
-
-_told_training_path = False
-
-
-def _training_path_notice(what):
-    """Training steps (run_nerf.py:942-1018, trainer.py:882-990) take the STAGED path: sampling and compositing run
-    on the HIP kernels - compositing with its HIP backward (inerf_composite_backward) - and each network is one
-    autograd node (kernels.mlp_train): fused HIP forward that keeps the activations, HIP input-gradient chain, weight
-    gradients by the split-K MFMA kernel.  A network outside the fused architecture, ``INERF_TRAIN_MLP=layered`` and a batch
-    outside the f16 range go layer by layer through the exact-fp32 MFMA kernels (layered.py: HIP forward and backward too);
-    ``INERF_TRAIN_MLP=torch`` evaluates the modules' torch ``forward`` under autograd (debugging).  Said once per process."""
-    global _told_training_path
-    if not _told_training_path:
-        import warnings
-        warnings.warn(f"{what}: gradients requested - using the staged training path (HIP sampling, HIP compositing and "
-                      "network kernels with HIP backward).  Render under torch.no_grad() for the fully fused path.")
-        _told_training_path = True
-
-
-def _train_desc(desc):
-    """Descriptor for the fused training evaluation of a fusable network, or None when the layers are evaluated one by one:
-    ``INERF_TRAIN_MLP`` = ``hip`` (default: fused split-precision forward that keeps the activations + HIP backward, kernels.mlp_train) |
-    ``layered`` (exact fp32 throughout, like the reference's run_nerf.py:942-1018: the fp32 MFMA layer kernels, forward and backward) |
-    ``torch`` (the modules' own torch ``forward`` under autograd: the comparison baseline of the gradient tests)."""
-    import os
-    if desc is None or os.environ.get("INERF_TRAIN_MLP", "hip") in ("torch", "layered"):
-        return None
-    return desc           # precision f32: exact-fp32 forward values, split-precision saved activations + HIP backward (kernels.mlp_train)
-
-
-FP32_LAYERS_NOTE = "Evaluating this batch with the fp32 layer kernels instead."
-
-
-def _train_query(train_desc, fn, ray_batch, z_vals, endpoint=False):
-    """raw for a training step through kernels.mlp_train; None if this batch left the f16 range (the caller then evaluates it
-    layer by layer in exact fp32: ``_layered_spec``)."""
-    try:
-        return kernels.mlp_train(train_desc, fn, ray_batch, z_vals, endpoint)
-    except FloatingPointError as e:
-        import warnings
-        warnings.warn(f"{e}  {FP32_LAYERS_NOTE}")
-        return None
-
-
-def _layered_spec(fn, embed_fn, embeddirs_fn, with_dirs=True):
-    """layered.Spec when ``fn`` can be evaluated layer by layer on the fp32 MFMA kernels (any D / W / skips of this package's
-    networks, fed by this package's encoders), else None.  ``INERF_TRAIN_MLP=torch`` keeps torch's layers for a training step
-    (the comparison baseline of the gradient tests)."""
-    import os
-    if os.environ.get("INERF_TRAIN_MLP", "hip") == "torch" and _wants_grad(fn):
-        return None
-    spec = layered.spec_for(fn, embed_fn, embeddirs_fn if with_dirs else None)
-    if spec is None or spec.use_viewdirs != bool(with_dirs):
-        return None
-    return spec
-
-
-def _run_network_torch(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk):
-    """run_nerf.py:42-56 as written there: torch-evaluated embedding, ``fn`` applied in ``netchunk`` pieces.  Used for
-    networks the fused kernel does not implement and for training steps (autograd records the layers)."""
-    flat = torch.reshape(inputs, [-1, inputs.shape[-1]])
-    emb = embed_fn(flat)
-    if viewdirs is not None:
-        dirs = viewdirs[:, None].expand(inputs.shape)
-        emb = torch.cat([emb, embeddirs_fn(torch.reshape(dirs, [-1, dirs.shape[-1]]))], -1)
-    out = torch.cat([fn(emb[i:i + netchunk]) for i in range(0, emb.shape[0], netchunk)], 0) if netchunk else fn(emb)
-    return torch.reshape(out, list(inputs.shape[:-1]) + [out.shape[-1]])
-
-
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):
     """Encode ``inputs[..., 3]`` (+ ``viewdirs[N, 3]``) and apply network ``fn`` - run_nerf.py:42-56.
 
@@ -255,31 +173,7 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
     bounded the reference's activation memory and does not affect results).  Any other ``fn`` is
     called like the reference does, on the torch-evaluated embedding.
     """
-    desc = _fusable(fn, embed_fn, embeddirs_fn) if viewdirs is not None else None
-    if desc is None or _wants_grad(fn):
-        # another depth / width / skip list, no view directions, or gradients wanted for arbitrary points: layer by layer on the
-        # fp32 MFMA kernels (differentiable w.r.t. the parameters); a foreign callable is called as the reference calls it
-        if desc is not None:
-            _training_path_notice("run_network")
-        spec = _layered_spec(fn, embed_fn, embeddirs_fn, viewdirs is not None) if inputs.is_cuda else None
-        if spec is not None:
-            return layered.evaluate_points(spec, fn, inputs, viewdirs)
-        return _run_network_torch(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk)
-    # arbitrary points: one "ray" per point with origin = point, direction = 0, depth 0 -> o + 0*0 = o
-    pts = torch.reshape(inputs, [-1, 3]).float()
-    dirs = torch.reshape(viewdirs[:, None].expand(inputs.shape), [-1, 3]).float()
-    rays = torch.zeros(pts.shape[0], _capi.RAY_FLOATS, dtype=torch.float32, device=pts.device)
-    rays[:, 0:3], rays[:, 8:11] = pts, dirs
-    z = torch.zeros(pts.shape[0], 1, dtype=torch.float32, device=pts.device)
-
-    def run(d):
-        status = kernels._new_status(pts) if d.precision == _capi.PREC_F16X3 else None
-        out = kernels.encode_mlp(d, packing.packed_for_module(fn, d, pts.device), rays, z, status=status)
-        kernels.check_f16_range(status, "run_network")
-        return out
-
-    raw = kernels.with_f32_fallback(desc, run)
-    return torch.reshape(raw, list(inputs.shape[:-1]) + [raw.shape[-1]])
+    return render_core.run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk, endpoint=False)
 
 
 def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False):
@@ -370,104 +264,44 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             nz = torch.Tensor(np.random.rand(n, s) * raw_noise_std).to(dev)
         return nz
 
+    noise_c = noise(N_samples)
+    u = _draw_u(n, N_importance, perturb == 0., pytest, dev) if (N_importance > 0 and not drawn_perturb) else None
+    noise_f = noise(N_samples + N_importance) if N_importance > 0 else None
+    fine_net = network_fine if network_fine is not None else network_fn
     train_desc = None
     if desc is not None and _wants_grad(network_fn, network_fine):
         _training_path_notice("render_rays")
         train_desc, desc = _train_desc(desc), None
     if desc is not None:
-        noise_c = noise(N_samples)
-        u = _draw_u(n, N_importance, perturb == 0., pytest, dev) if (N_importance > 0 and not drawn_perturb) else None
-        noise_f = noise(N_samples + N_importance) if N_importance > 0 else None
-        fine_net = network_fine if network_fine is not None else network_fn
         draw = draws.args(base, raw_noise_std if drawn_noise else 0., perturb=True if drawn_perturb else False) if (
             drawn_perturb or drawn_noise) else None
-
-        def run(d):
-            res = kernels.render_rays_fused(
-                d, packing.packed_for_module(network_fn, d, dev),
-                packing.packed_for_module(fine_net, d, dev) if N_importance > 0 else None,
-                ray_batch, N_samples, N_importance, t_vals, u, t_rand, noise_c, noise_f, white_bkgd, lindisp,
-                want_raw_coarse=retraw and N_importance == 0, want_raw_fine=retraw, draw=draw)
-            # eval-mode chunks of a frame (no RNG draws to repeat) leave the check to batchify_rays' end-of-frame one; so do chunks
-            # whose draws come from the kernels (a second render of the chunk repeats them: the step has not advanced)
-            kernels.check_f16_range(res.pop("status", None), "render_rays", deferrable=t_rand is None and noise_c is None)
-            return res
-
-        o = kernels.with_f32_fallback(desc, run)
-        lvl = "fine" if N_importance > 0 else "coarse"
-        ret = {rk: o[f"{ok}_{lvl}"] for rk, ok in _RET_MAP}
-        if retraw:
-            ret["raw"] = o["raw_" + lvl]
-        if N_importance > 0:
-            for rk, ok in _RET_0:
-                ret[rk] = o[ok + "_coarse"]
-            ret["z_std"] = o["z_std"]
+        o = render_core.render_fused(desc, network_fn, fine_net, "render_rays", ray_batch, N_samples, N_importance, t_vals, u, t_rand,
+                                     noise_c, noise_f, white_bkgd=white_bkgd, lindisp=lindisp,
+                                     want_raw_coarse=retraw and N_importance == 0, want_raw_fine=retraw, draw=draw)
     else:
         # a network outside the fused architecture, a user-supplied one, or a training step: the stages run on the HIP kernels
         # (compositing differentiably); the network through kernels.mlp_train, the fp32 layer kernels (layered.py) or - a foreign
-        # callable - as given
-        rays_o, rays_d, viewdirs = ray_batch[:, 0:3], ray_batch[:, 3:6].contiguous(), ray_batch[:, -3:]
-
-        def staged(td):
-            def query(z, fn):
-                raw = _train_query(td, fn, ray_batch, z) if td is not None else None        # nq's encoders
-                if raw is None:
-                    spec = _layered_spec(fn, nq.embed_fn, nq.embeddirs_fn) if nq is not None else None
-                    if spec is not None:        # any depth / width / skips, or a batch outside the f16 range: fp32 layer kernels
-                        raw = layered.evaluate(spec, fn, ray_batch, z)
-                    else:                       # a foreign network or query function: called as the reference calls it
-                        pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
-                        raw = network_query_fn(pts, viewdirs, fn)
-                return raw
-
-            z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, lindisp, draw=draws.args(base) if drawn_perturb else None)
-            raw = query(z_vals, network_fn)
-            c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples), white_bkgd,
-                                  draw=draws.args(base, raw_noise_std) if drawn_noise else None)
-            ret = {rk: c[ok] for rk, ok in _RET_MAP}
-            if N_importance > 0:
-                c0 = c
-                u = None if drawn_perturb else _draw_u(n, N_importance, perturb == 0., pytest, dev)
-                z_samples, z_vals, z_std = kernels.sample_fine(z_vals, c0["weights"], u, N_importance,
-                                                               draw=draws.args(base) if drawn_perturb else None)
-                raw = query(z_vals, network_fn if network_fine is None else network_fine)
-                c = kernels.composite(raw.float(), z_vals, rays_d, noise(N_samples + N_importance), white_bkgd,
-                                      draw=draws.args(base, raw_noise_std, fine=True) if drawn_noise else None)
-                ret = {rk: c[ok] for rk, ok in _RET_MAP}
-                for rk, ok in _RET_0:
-                    ret[rk] = c0[ok]
-                ret["z_std"] = z_std
-            if retraw:
-                ret["raw"] = raw
-            return ret
-
-        if train_desc is None:
-            ret = staged(None)
-        else:
-            # ONE read of the f16 range words per training forward, after every launch of the batch has been enqueued (a read
-            # after each network leaves the GPU idle while the host prepares the next launches).  If it trips, the whole batch
-            # is evaluated again layer by layer in exact fp32 (layered.evaluate: HIP forward and backward, no range limit) - with
-            # the random draws repeated, so it consumes the RNG like the reference would.
-            redraw = ((raw_noise_std > 0. and not drawn_noise) or (perturb > 0. and N_importance > 0 and not drawn_perturb)) and not kernels._capturing()
-            rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None) if redraw else None
-            np_state = np.random.get_state() if pytest else None
-            try:
-                with kernels.deferred_range_checks("render_rays (training step)"):
-                    ret = staged(train_desc)
-            except FloatingPointError as e:
-                import warnings
-                warnings.warn(f"{e}  {FP32_LAYERS_NOTE}")
-                if rng is not None:
-                    torch.set_rng_state(rng[0])
-                    if rng[1] is not None:
-                        torch.cuda.set_rng_state(rng[1], dev)
-                if np_state is not None:
-                    np.random.set_state(np_state)
-                ret = staged(None)
-    if verbose and not kernels._capturing():   # the reference's DEBUG nan/inf scan (run_nerf.py:524-526); each check is a device sync
-        for k in ret:
-            if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
-                print(f"! [Numerical Error] {k} contains nan or inf.")
+        # callable or query function - as the reference calls it
+        dr = {"perturb": draws.args(base) if drawn_perturb else None,
+              "noise_c": draws.args(base, raw_noise_std) if drawn_noise else None,
+              "noise_f": draws.args(base, raw_noise_std, fine=True) if drawn_noise else None}
+        encoders = (nq.embed_fn, nq.embeddirs_fn) if nq is not None else None
+        foreign = lambda pts, viewdirs, fn, endpoint: network_query_fn(pts, viewdirs, fn)
+        o = render_core.training_step(
+            lambda td: render_core.staged_pass(ray_batch, t_vals, (t_rand, noise_c, u, noise_f), dr, (network_fn, fine_net),
+                                               render_core.make_query(td, ray_batch, encoders, foreign), N_importance, white_bkgd,
+                                               lindisp),
+            train_desc, "render_rays")
+    lvl = "fine" if N_importance > 0 else "coarse"
+    ret = {rk: o[f"{ok}_{lvl}"] for rk, ok in _RET_MAP}
+    if retraw:
+        ret["raw"] = o["raw_" + lvl]
+    if N_importance > 0:
+        for rk, ok in _RET_0:
+            ret[rk] = o[ok + "_coarse"]
+        ret["z_std"] = o["z_std"]
+    if verbose:       # the reference's DEBUG nan/inf scan (run_nerf.py:524-526)
+        render_core.report_non_finite(ret)
     if (drawn_perturb or drawn_noise) and ray_base is None:      # the whole batch was this one call: the next call draws at the next step
         draws.advance()
     return ret
@@ -493,19 +327,13 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """Render rays in chunks - run_nerf.py:59-71.  Results do not depend on ``chunk`` - so eval-mode frames of the fused path
     are rendered in FEWER, larger launches than ``chunk`` asks for (``_coalesced``; ``INERF_COALESCE_BYTES=0`` keeps the caller's).
 
-    The split-precision kernel's range words are read ONCE per call, after the last chunk has been enqueued
-    (kernels.deferred_range_checks): a frame is one host synchronisation, not one per chunk.  Chunks whose word reports an
-    out-of-range activation - and only those - are rendered again with the exact fp32 kernel (only eval-mode chunks defer,
-    so no random draw is repeated; chunks that draw random numbers check and fall back inside render_rays)."""
+    The loop is render_core.render_chunks: the f16 range words are read ONCE per call, and the chunks that left the range - and
+    only those - are rendered again with the exact fp32 kernel.  With ``draws`` every chunk draws at the same step with its first
+    global ray index as base; the step advances once, after the last chunk (render_core.advance_after)."""
     draws = kwargs.get("draws")
     if draws is not None and (kwargs.get("perturb", 0.) > 0. or kwargs.get("raw_noise_std", 0.) > 0.):
-        # every chunk draws at the same step with its first global ray index as base (the result does not depend on `chunk`); the step
-        # advances once, after the last chunk - a chunk rendered again in exact fp32 below repeats its own draws
         # (a caller that renders a band of a larger batch passes the band's start as ray_base)
-        try:
-            return _batchify_rays(rays_flat, chunk, kwargs)
-        finally:
-            draws.advance()
+        return render_core.advance_after(draws, _batchify_rays, rays_flat, chunk, kwargs)
     return _batchify_rays(rays_flat, chunk, kwargs)
 
 
@@ -513,44 +341,9 @@ def _batchify_rays(rays_flat, chunk, kwargs):
     kwargs = dict(kwargs)
     base0 = int(kwargs.pop("ray_base", None) or 0)
     based = (lambda i: {"ray_base": base0 + i}) if kwargs.get("draws") is not None else (lambda i: {})
-    big = _coalesced(rays_flat, chunk, kwargs)
-    if big > chunk:
-        # eval mode, fused networks, no raw: nothing depends on the chunk boundaries (results are bit-identical for any chunking), so
-        # the frame goes through in as few launches as the workspace cap allows (kernels.coalesced_chunk) - with one f16 range word
-        # per CALLER's chunk (kernels.chunked_status), so that a chunk that leaves the range is still the only one rendered again
-        rets = []
-        with kernels.deferred_range_checks("render", raise_on_trip=False) as block, kernels.chunked_status(chunk):
-            for j, i in enumerate(range(0, rays_flat.shape[0], big)):
-                block.tag = j
-                rets.append(render_rays(rays_flat[i:i + big], **kwargs, **based(i)))
-        out = {k: (rets[0][k] if len(rets) == 1 else torch.cat([r[k] for r in rets], 0)) for k in rets[0]}
-        if block.tripped:
-            # tags: (piece, word) of a piece with one word per caller's chunk, or the piece itself (it held no more than one chunk)
-            spans = sorted({(t[0] * big + t[1] * chunk, chunk) if isinstance(t, tuple) else (t * big, big) for t in block.tripped})
-            kernels.warn_f32_fallback(f"render: {len(spans)} of {-(-rays_flat.shape[0] // chunk)} chunks left the f16 range of the "
-                                      "split-precision MLP kernel.")
-            with _capi.forced_precision(_capi.PREC_F32):
-                for i, n_i in spans:
-                    again = render_rays(rays_flat[i:i + n_i], **kwargs, **based(i))
-                    for k in out:
-                        out[k][i:i + n_i] = again[k]
-        return out
-    starts = list(range(0, rays_flat.shape[0], chunk))
-    rets = []
-    with kernels.deferred_range_checks("render", raise_on_trip=False) as block:
-        for j, i in enumerate(starts):
-            block.tag = j
-            rets.append(render_rays(rays_flat[i:i + chunk], **kwargs, **based(i)))
-    if block.tripped:
-        kernels.warn_f32_fallback(f"render: {len(block.tripped)} of {len(starts)} chunks left the f16 range of the split-precision "
-                                  "MLP kernel.")
-        with _capi.forced_precision(_capi.PREC_F32):
-            for j in block.tripped:
-                rets[j] = render_rays(rays_flat[starts[j]:starts[j] + chunk], **kwargs, **based(starts[j]))
-    if not rets:
-        return {}
-    return {k: (rets[0][k] if len(rets) == 1 else torch.cat([r[k] for r in rets], 0)) for k in rets[0]}
-
+    # (render_rays is looked up when a piece is rendered: callers and tests wrap the module's function)
+    return render_core.render_chunks(lambda i, count: render_rays(rays_flat[i:i + count], **kwargs, **based(i)),
+                                     rays_flat.shape[0], chunk, _coalesced(rays_flat, chunk, kwargs), "render")
 
 def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
            c2w_staticcam=None, **kwargs):

@@ -9,16 +9,18 @@ Mirrors, with identical names / argument meaning / returned keys (citations rela
   SSRRenderMixin.render_rays / volumetric_rendering / create_ssr
                            training/trainer.py:693-715 / 717-808 / 811-846
 ``SSRTrainer`` keeps its data loading, losses and logging; it only has to inherit the mixin (or
-assign the three methods) - see INTEGRATION.md.  All arithmetic runs in ``libinerf.so``.
+assign the three methods) - see INTEGRATION.md.  All arithmetic runs in ``libinerf.so``; the control
+path shared with ``object_level.py`` - fusability, the chunk loop with its f16 range fallback, the
+staged pass of a training step - is ``render_core.py``.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _capi, kernels, layered, packing
-from .object_level import (FP32_LAYERS_NOTE, Embedder, _layered_spec, _run_network_torch, _train_desc, _train_query, _training_path_notice,
-                           _wants_grad)
+from . import _capi, kernels, render_core
+from .object_level import Embedder
+from .render_core import _fusable, _train_desc, _training_path_notice, _unfused_notice, _wants_grad
 from .losses import compute_intrinsic_loss_ssr as compute_intrinsic_loss, ssr_step_loss  # noqa: F401  (training_utils.py:179-207, trainer.py:923-988)
 
 __all__ = ["get_embedder", "Semantic_NeRF", "run_network", "raw2outputs", "sample_pdf", "create_rays",
@@ -106,62 +108,12 @@ class Semantic_NeRF(nn.Module):
         return torch.cat(parts, -1)
 
 
-_told_unfused = False
-
-
-def _unfused_notice(what):
-    """Said once per process (the object-level front-end's staged branch does the same for foreign networks)."""
-    global _told_unfused
-    if not _told_unfused:
-        import warnings
-        warnings.warn(f"{what}: network / encoders outside the fused kernels' architecture (D=8, W=256, skips=[4], multires<=10, "
-                      "multires_views<=4): HIP sampling and compositing, the networks layer by layer on the fp32 MFMA kernels "
-                      "(a foreign callable: through its own forward).")
-        _told_unfused = True
-
-
-def _fusable(fn, embed_fn, embeddirs_fn):
-    if not hasattr(fn, "fused_desc"):
-        return None
-    desc = fn.fused_desc()
-    if desc is None or not isinstance(embed_fn, Embedder) or not isinstance(embeddirs_fn, Embedder):
-        return None
-    if embed_fn.n_freqs != desc.l_xyz or embeddirs_fn.n_freqs != desc.l_dir or embeddirs_fn.scalar_factor != 1.0:
-        return None
-    desc.xyz_div = embed_fn.scalar_factor
-    return desc
-
-
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64, show_endpoint=False):
     """Encode + apply the network - model_utils.py:19-35.  ``fn`` is a Semantic_NeRF (fused HIP launch) or
     any callable on the embedded tensor (called as the reference does).  ``show_endpoint`` is what the
     reference expresses as ``lambda x: net(x, self.endpoint_feat)`` (trainer.py:770)."""
-    desc = _fusable(fn, embed_fn, embeddirs_fn) if viewdirs is not None else None
-    if desc is None or _wants_grad(fn):
-        # another netdepth / netwidth (trainer.py:811-846 builds what the YAML says), or gradients for arbitrary points: layer by
-        # layer on the fp32 MFMA kernels (layered.py).  Any other callable is called as the reference calls it (model_utils.py:19-35)
-        if desc is not None:
-            _training_path_notice("run_network")
-        spec = _layered_spec(fn, embed_fn, embeddirs_fn, viewdirs is not None) if inputs.is_cuda else None
-        if spec is not None:
-            return layered.evaluate_points(spec, fn, inputs, viewdirs, endpoint=show_endpoint)
-        call = (lambda x: fn(x, True)) if show_endpoint else fn          # trainer.py:770
-        return _run_network_torch(inputs, viewdirs, call, embed_fn, embeddirs_fn, netchunk)
-    pts = torch.reshape(inputs, [-1, 3]).float()
-    dirs = torch.reshape(viewdirs[:, None].expand(inputs.shape), [-1, 3]).float()
-    rays = torch.zeros(pts.shape[0], _capi.RAY_FLOATS, dtype=torch.float32, device=pts.device)
-    rays[:, 0:3], rays[:, 8:11] = pts, dirs
-    z = torch.zeros(pts.shape[0], 1, dtype=torch.float32, device=pts.device)
-
-    def run(d):
-        status = kernels._new_status(pts) if d.precision == _capi.PREC_F16X3 else None
-        out = kernels.encode_mlp(d, packing.packed_for_module(fn, d, pts.device), rays, z, endpoint=show_endpoint,
-                                 status=status)
-        kernels.check_f16_range(status, "run_network")
-        return out
-
-    raw = kernels.with_f32_fallback(desc, run)
-    return torch.reshape(raw, list(inputs.shape[:-1]) + [raw.shape[-1]])
+    return render_core.run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk, endpoint=show_endpoint,
+                                   foreign=(lambda x: fn(x, True)) if show_endpoint else None)          # trainer.py:770
 
 
 def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, enable_semantic=True, num_sem_class=0,
@@ -248,7 +200,7 @@ def create_rays(num_rays, Ts_c2w, height, width, fx, fy, cx, cy, near, far, c2w_
 
 
 def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None, with_ray_base=False):
-    """training_utils.py:5-17.  As in object_level.batchify_rays the chunks' f16 range words are read together after the
+    """training_utils.py:5-17 on render_core.render_chunks: the chunks' f16 range words are read together after the
     last chunk (one host synchronisation per frame) and only the chunks that left the range are rendered again in exact
     fp32.  ``coalesce_to`` (SSRRenderMixin.render_rays, eval-mode frames whose result cannot depend on the chunk boundaries):
     rays per call instead of ``chunk``; the launches keep one f16 range word per ``chunk`` rays, so a chunk that leaves the range is still the
@@ -257,39 +209,7 @@ def batchify_rays(render_fn, rays_flat, chunk=1024 * 32, coalesce_to=None, with_
     def piece(i, count):
         return render_fn(rays_flat[i:i + count], ray_base=i) if with_ray_base else render_fn(rays_flat[i:i + count])
 
-    if coalesce_to is not None and coalesce_to > chunk:
-        rets = []
-        with kernels.deferred_range_checks("render_rays", raise_on_trip=False) as block, kernels.chunked_status(chunk):
-            for j, i in enumerate(range(0, rays_flat.shape[0], coalesce_to)):
-                block.tag = j
-                rets.append(piece(i, coalesce_to))
-        out = {k: torch.cat([r[k] for r in rets], 0) for k in rets[0]}
-        if block.tripped:     # one range word per caller's chunk (kernels.chunked_status): only the chunks that left the range, in exact fp32
-            spans = sorted({(t[0] * coalesce_to + t[1] * chunk, chunk) if isinstance(t, tuple) else (t * coalesce_to, coalesce_to)
-                            for t in block.tripped})
-            kernels.warn_f32_fallback(f"render_rays: {len(spans)} of {-(-rays_flat.shape[0] // chunk)} chunks left the f16 range of the "
-                                      "split-precision MLP kernel.")
-            with _capi.forced_precision(_capi.PREC_F32):
-                for i, n_i in spans:
-                    again = piece(i, n_i)
-                    for k in out:
-                        out[k][i:i + n_i] = again[k]
-        return out
-    starts = list(range(0, rays_flat.shape[0], chunk))
-    rets = []
-    with kernels.deferred_range_checks("render_rays", raise_on_trip=False) as block:
-        for j, i in enumerate(starts):
-            block.tag = j
-            rets.append(piece(i, chunk))
-    if block.tripped:
-        kernels.warn_f32_fallback(f"render_rays: {len(block.tripped)} of {len(starts)} chunks left the f16 range of the "
-                                  "split-precision MLP kernel.")
-        with _capi.forced_precision(_capi.PREC_F32):
-            for j in block.tripped:
-                rets[j] = piece(starts[j], chunk)
-    if not rets:
-        return {}
-    return {k: torch.cat([r[k] for r in rets], 0) for k in rets[0]}
+    return render_core.render_chunks(piece, rays_flat.shape[0], chunk, max(chunk, coalesce_to or 0), "render_rays")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -316,17 +236,12 @@ class SSRRenderMixin:
 
     def render_rays(self, flat_rays):
         ray_shape = flat_rays.shape
-        draws = self.draws
-        if draws is not None and bool(self.training) and (self.perturb > 0. or self.raw_noise_std > 0.):
-            # (eval-mode frames and renders that draw nothing leave the step alone: it counts drawing renders) every chunk draws at the same step, based at its first global ray index; the step advances once, after the last chunk (a
-            # chunk rendered again in exact fp32 repeats its own draws)
-            try:
-                all_ret = batchify_rays(self.volumetric_rendering, flat_rays, self.chunk,
-                                        self._coalesced(flat_rays), with_ray_base=True)
-            finally:
-                draws.advance()
+        loop = (self.volumetric_rendering, flat_rays, self.chunk, self._coalesced(flat_rays))
+        if self.draws is not None and bool(self.training) and (self.perturb > 0. or self.raw_noise_std > 0.):
+            # (eval-mode frames and renders that draw nothing leave the step alone: it counts drawing renders)
+            all_ret = render_core.advance_after(self.draws, batchify_rays, *loop, with_ray_base=True)
         else:
-            all_ret = batchify_rays(self.volumetric_rendering, flat_rays, self.chunk, self._coalesced(flat_rays))      # one host synchronisation per frame
+            all_ret = batchify_rays(*loop)      # one host synchronisation per frame
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], list(ray_shape[:-1]) + list(all_ret[k].shape[1:]))
         return all_ret
@@ -556,33 +471,25 @@ class SSRRenderMixin:
                   "noise_f": draws.args(base, std, fine=True) if drawn_noise else None,
                   "fused": draws.args(base, std if drawn_noise else 0., perturb=drawn_perturb)}
 
-        def run(d):
-            res = kernels.render_rays_fused(
-                d, packing.packed_for_module(self.ssr_net_coarse, d, dev),
-                packing.packed_for_module(self.ssr_net_fine, d, dev) if self.N_importance > 0 else None,
-                ray_batch, self.N_samples, self.N_importance, t_vals, u, t_rand, noise_c, noise_f,
-                white_bkgd=self.white_bkgd, endpoint=ep, want_raw_coarse=self.return_raw, want_raw_fine=self.return_raw,
-                want_sem=bool(self.enable_semantic), draw=None if dr is None else dr["fused"])
-            kernels.check_f16_range(res.pop("status", None), "volumetric_rendering", deferrable=t_rand is None and noise_c is None)
-            return res
-
-        if desc is None:
-            o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
-        elif _wants_grad(self.ssr_net_coarse, self.ssr_net_fine):
+        train_desc = None
+        if desc is not None and _wants_grad(self.ssr_net_coarse, self.ssr_net_fine):
             _training_path_notice("volumetric_rendering")
-            td = _train_desc(desc)
-            if td is None:
-                o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
-            else:       # one read of both networks' f16 range words, after the whole forward has been enqueued (object_level.render_rays)
-                try:
-                    with kernels.deferred_range_checks("volumetric_rendering (training step)"):
-                        o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, td, dr)
-                except FloatingPointError as e:
-                    import warnings
-                    warnings.warn(f"{e}  {FP32_LAYERS_NOTE}")
-                    o = self._staged(ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, None, dr)
-        else:
-            o = kernels.with_f32_fallback(desc, run)
+            train_desc, desc = _train_desc(desc), None
+        if desc is not None:
+            o = render_core.render_fused(desc, self.ssr_net_coarse, self.ssr_net_fine, "volumetric_rendering", ray_batch, self.N_samples,
+                                         self.N_importance, t_vals, u, t_rand, noise_c, noise_f, white_bkgd=self.white_bkgd, endpoint=ep,
+                                         want_raw_coarse=self.return_raw, want_raw_fine=self.return_raw,
+                                         want_sem=bool(self.enable_semantic), draw=None if dr is None else dr["fused"])
+        else:       # stage by stage (render_core.staged_pass); a training step reads both networks' f16 range words once
+            foreign = lambda pts, viewdirs, fn, endpoint: run_network(pts, viewdirs, fn, self.embed_fn, self.embeddirs_fn, self.netchunk,
+                                                                      show_endpoint=endpoint)
+            o = render_core.training_step(
+                lambda td: render_core.staged_pass(ray_batch, t_vals, (t_rand, noise_c, u, noise_f), dr,
+                                                   (self.ssr_net_coarse, self.ssr_net_fine),
+                                                   render_core.make_query(td, ray_batch, (self.embed_fn, self.embeddirs_fn), foreign),
+                                                   self.N_importance, self.white_bkgd,
+                                                   n_classes=self.num_valid_semantic_class if self.enable_semantic else 0, endpoint=ep),
+                train_desc, "volumetric_rendering")
         ret = {}
         if self.return_raw:
             ret["raw_coarse"] = o["raw_coarse"]
@@ -600,53 +507,11 @@ class SSRRenderMixin:
                 ret["raw_fine"] = o["raw_fine"]
             if ep:
                 ret["feat_map_fine"] = o["feat_fine"]
-        if self.check_numerics and not kernels._capturing():      # (a host read per key: not possible while a HIP graph records)
-            for k in ret:
-                if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
-                    print(f"! [Numerical Error] {k} contains nan or inf.")
+        if self.check_numerics:
+            render_core.report_non_finite(ret)
         if dr is not None and ray_base is None:
             draws.advance()
         return ret
-
-    def _staged(self, ray_batch, t_vals, t_rand, noise_c, u, noise_f, ep, train_desc=None, dr=None):
-        """trainer.py:717-808 stage by stage, for training steps: HIP sampling, HIP compositing with its HIP backward, each
-        network one autograd node with HIP forward and backward (kernels.mlp_train; torch ``forward`` when ``train_desc`` is
-        None).  Same keys as kernels.render_rays_fused."""
-        rays_o, rays_d, viewdirs = ray_batch[:, 0:3], ray_batch[:, 3:6].contiguous(), ray_batch[:, -3:]
-        c_sem = self.num_valid_semantic_class if self.enable_semantic else 0
-        dr = dr or {"perturb": None, "noise_c": None, "noise_f": None}      # (drawn in the kernels: volumetric_rendering)
-
-        def query(z, fn, endpoint=False):
-            raw = _train_query(train_desc, fn, ray_batch, z, endpoint) if train_desc is not None else None
-            if raw is None:
-                spec = _layered_spec(fn, self.embed_fn, self.embeddirs_fn)
-                if spec is not None:            # another netdepth / netwidth, or a batch outside the f16 range: fp32 layer kernels
-                    raw = layered.evaluate(spec, fn, ray_batch, z, endpoint)
-                else:
-                    pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
-                    raw = run_network(pts, viewdirs, fn, self.embed_fn, self.embeddirs_fn, self.netchunk, show_endpoint=endpoint)
-            return raw
-
-        z_vals = kernels.sample_coarse(ray_batch, t_vals, t_rand, False, draw=dr["perturb"])
-        raw = query(z_vals, self.ssr_net_coarse)
-        c = kernels.composite(raw, z_vals, rays_d, noise_c, self.white_bkgd, n_classes=c_sem, draw=dr["noise_c"])
-        o = {k + "_coarse": v for k, v in c.items()}
-        o["raw_coarse"] = raw
-        if self.N_importance > 0:
-            # the resampled depths carry no gradient (z_samples.detach(), trainer.py:762)
-            z_samples, z_fine, z_std = kernels.sample_fine(z_vals, c["weights"].detach(), u, self.N_importance, draw=dr["perturb"])
-            raw = query(z_fine, self.ssr_net_fine, ep)
-            # the endpoint feature is the LAST 128 channels of raw (model_utils.py:99-103, a literal 128 there).  A foreign netwidth
-            # gives raw another width (W // 2 feature channels): the kernel's feature lanes only take the 256-wide network's layout,
-            # the reference's literal slice is evaluated as written for any other
-            native_feat = ep and raw.shape[-1] == 11 + c_sem + 128
-            f = kernels.composite(raw, z_fine, rays_d, noise_f, self.white_bkgd, n_classes=c_sem, feat_dim=128 if native_feat else 0,
-                                  draw=dr["noise_f"])
-            if ep and not native_feat:
-                f["feat"] = torch.sum(f["weights"][..., None] * raw[..., -128:], -2)
-            o.update({k + "_fine": v for k, v in f.items()})
-            o["raw_fine"], o["z_std"] = raw, z_std
-        return o
 
     def sample_data(self, step, rays, h, w, no_batching=True, mode="train"):
         """``SSRTrainer.sample_data`` (trainer.py:627-691).  With ``no_batching`` the draws are the reference's own
