@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40021
+#define INERF_ABI_VERSION 40022
 
 /* error codes */
 #define INERF_OK              0
@@ -992,10 +992,11 @@ int inerf_batch_assemble(const inerf_batch_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mesh extraction: the query lattice of a scene's oriented bounding box and the occupancy of a trained network on it
- * (SSR/extract_colour_mesh.py:149-185, SSR/geometry/occupancy.py:5-48), then - after marching cubes and the mesh cleaning, which
- * stay with the caller (skimage and open3d, on the returned array) - the vertex-colour pass (extract_colour_mesh.py:232-257): one ray
- * per mesh vertex (inerf_vertex_rays), ordinary inerf_render_rays launches, and the 8-bit colour of every vertex written on the
- * device (inerf_vertex_colours), so that three bytes per vertex travel to the host.
+ * (SSR/extract_colour_mesh.py:149-185, SSR/geometry/occupancy.py:5-48), then marching cubes, the map to scene coordinates, vertex
+ * normals and the removal of small components on the device (:186-219: inerf_mc_count, inerf_mc_emit, inerf_mesh_normals,
+ * inerf_mesh_clean, further down), then the vertex-colour pass (extract_colour_mesh.py:232-257): one ray per mesh vertex
+ * (inerf_vertex_rays), ordinary inerf_render_rays launches, and the 8-bit colour of every vertex written on the device
+ * (inerf_vertex_colours), so that three bytes per vertex travel to the host.
  * ------------------------------------------------------------------------------------------- */
 #define INERF_MAX_GRID_DIM 1024           /* points per lattice axis: dim^3 <= 2^30 fits the kernels' 32-bit point index */
 
@@ -1079,6 +1080,70 @@ int inerf_vertex_rays_host(const void* vertices /*[host]*/, int64_t v_stride, co
 int inerf_vertex_colours(const float* rgb, int64_t rgb_stride, const float* logits, int64_t logits_stride, int64_t n, int n_classes,
                          const unsigned char* colour_map /*[n_classes,3]*/, unsigned char* colours_out /*[n,3]*/,
                          int32_t* labels_out /*[n] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Marching cubes and mesh cleaning (csrc/mcubes.hip; SSR/extract_colour_mesh.py:186-219): from the occupancy lattice to welded
+ * vertices, int32 faces, fp64 vertex normals and a mesh without its small components, all on the device.  The triangulation is this
+ * project's own (csrc/mc_tables.h, generated by scripts/gen_mc_tables.py): it is watertight by construction
+ * and NOT skimage's Lewiner table, so vertex sets agree with skimage's but faces do not, and degenerate triangles are kept.
+ * No kernel waits for another workgroup: every scan is three launches, every atomic is an integer atomic, and the results have
+ * the same bytes on every run.  Every entry point checks its arguments before it makes any HIP call.
+ *
+ * Lattice: occ[nx, ny, nz] floats, the last axis fastest; 2 <= nx, ny, nz (INERF_E_INVALID below) <= INERF_MAX_GRID_DIM and
+ * nx * ny * nz <= 2^30 (INERF_E_UNSUPPORTED beyond).  Corner c = di | dj << 1 | dk << 2 of cube (i, j, k) is occ[i + di, j + dj,
+ * k + dk]; it is inside iff occ > level (a NaN is outside).  Lattice point (i, j, k) OWNS the up to three lattice edges towards
+ * +i, +j and +k; an edge whose ends differ in "inside" carries one vertex.
+ * ------------------------------------------------------------------------------------------- */
+
+/* bytes of workspace inerf_mc_count / inerf_mc_emit need for the shape (10 per lattice point and a little); a negative INERF_E_*
+ * for a shape outside the limits */
+int64_t inerf_mc_workspace_bytes(int nx, int ny, int nz);
+
+/* One tiled pass over the lattice (every value read from memory about once, neighbours through LDS) flags the owned edges of every
+ * point and stores the case and triangle count of every cube; two exclusive scans (block sums, one workgroup over the sums, add pass)
+ * turn them into vertex and triangle offsets in `workspace`.  totals_dev[3] (int64, device) = {vertices, triangles, non-finite lattice
+ * values}: the caller reads it once to size inerf_mc_emit's outputs - the only synchronisation of the stage - and refuses a lattice
+ * with non-finite values.  workspace: 256-byte aligned, inerf_mc_workspace_bytes(...) bytes (INERF_E_WORKSPACE if smaller). */
+int inerf_mc_count(const float* occ, int nx, int ny, int nz, float level, void* workspace, int64_t workspace_bytes,
+                   int64_t* totals_dev /*[3]*/, void* stream);
+
+/* The mesh of the lattice inerf_mc_count just saw (same occ, shape, level and workspace), n_vertices / n_triangles as it reported:
+ *   vertices_lattice [n_vertices, 3] floats: in the order owner lattice point (linear index), then axis; on the edge's axis
+ *     index + t with t = (level - v0) / (v1 - v0) in plain fp32 (v0 at the owner, v1 at its neighbour), the index elsewhere.
+ *     Vertices are welded by construction.  May be NULL when vertices_scene is given.
+ *   vertices_scene [n_vertices, 3] doubles, with `affine` [host, 12 doubles: a row-major 3 x 4 map]: row r =
+ *     ((A[r][0] x + A[r][1] y) + A[r][2] z) + A[r][3] of the lattice coordinate promoted to double.  Both NULL or both given (not checked for an empty mesh).
+ *   faces [n_triangles, 3] int32: in the order cube (linear index of its corner 0), then the table's order; geometric normals
+ *     (b - a) x (c - a) point towards lower values - outward for an occupancy, which inerf_vertex_rays relies on.
+ * Nothing is written beyond n_vertices rows and n_triangles rows.  INERF_E_UNSUPPORTED: n_vertices > 2^31 - 1 or
+ * n_triangles > (2^31 - 1) / 3. */
+int inerf_mc_emit(const float* occ, int nx, int ny, int nz, float level, const void* workspace, int64_t workspace_bytes,
+                  const double* affine /*[host] 12 or NULL*/, int64_t n_vertices, int64_t n_triangles, float* vertices_lattice,
+                  double* vertices_scene, int32_t* faces, void* stream);
+
+/* bytes of workspace inerf_mesh_normals / inerf_mesh_clean need; a negative INERF_E_* for sizes outside the limits above */
+int64_t inerf_mesh_workspace_bytes(int64_t n_vertices, int64_t n_triangles);
+
+/* normals_out [n_vertices, 3] doubles: per vertex the fp64 sum, in ASCENDING TRIANGLE INDEX, of the un-normalised cross products
+ * (b - a) x (c - a) of its triangles, divided by its length sqrt((x x + y y) + z z); a zero sum stays zero.  open3d's
+ * compute_vertex_normals as far as it is known here.  Incident triangles are counted with integer atomics,
+ * scanned, filled into slots and sorted per vertex (in registers up to 4 * kMcMaxEdgeTriangles, the most a marching-cubes vertex
+ * has), so the bytes do not depend on the run.  A triangle with an index outside [0, n_vertices) contributes nothing. */
+int inerf_mesh_normals(const double* vertices /*[n_vertices,3]*/, int64_t n_vertices, const int32_t* faces /*[n_triangles,3]*/,
+                       int64_t n_triangles, void* workspace, int64_t workspace_bytes, double* normals_out, void* stream);
+
+/* open3d_utils.clean_mesh (SSR/visualisation/open3d_utils.py:175-201): connected components by lock-free union-find over the
+ * vertices (the label of a component is its smallest vertex index), triangles per component by integer atomics, then
+ *   keep_single_cluster == 0: triangles of components with fewer than min_triangles triangles are dropped;
+ *   keep_single_cluster != 0: only the component with the most triangles stays (a tie: the lowest label); min_triangles is not read;
+ * vertices no kept triangle names are dropped.  Both compactions keep the order; faces_out [<= n_triangles, 3] is re-indexed.  Up to
+ * three per-vertex arrays of three columns (one float, two double: lattice vertices, scene vertices, normals) are compacted with the
+ * same mask: each input NULL with its output, or both given.  Outputs are sized for the input counts and must not overlap inputs.
+ * totals_dev[4] (int64, device) = {vertices kept, triangles kept, components that own a triangle, components kept}. */
+int inerf_mesh_clean(const int32_t* faces /*[n_triangles,3]*/, int64_t n_vertices, int64_t n_triangles, int64_t min_triangles,
+                     int keep_single_cluster, const float* rows_f32, const double* rows_f64_a, const double* rows_f64_b,
+                     void* workspace, int64_t workspace_bytes, int32_t* faces_out, float* out_f32, double* out_f64_a,
+                     double* out_f64_b, int64_t* totals_dev /*[4]*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Validation metrics (csrc/eval.hip): the label and entropy maps of a rendered frame (SSR/training/trainer.py:1244-1245) and the

@@ -3,8 +3,9 @@
   object_level   drop-in for object_level/run_nerf.py + run_nerf_helpers.py (render, render_rays, ...)
   ssr            drop-in for SSR/ + train_SSR_main.py's render path (SSRRenderMixin, Semantic_NeRF, ...)
   losses         the trainers' loss terms, one forward and one backward launch (compute_intrinsic_loss, *_step_loss)
-  geometry       mesh extraction: query lattice, occupancy grid, vertex rays and 8-bit vertex colours (grid_within_bound,
-                 make_3D_grid, occupancy_grid, vertex_rays, vertex_colours)
+  geometry       mesh extraction: query lattice, occupancy grid, marching cubes, normals, cleaning, vertex rays, 8-bit vertex colours and
+                 the PLY (grid_within_bound, make_3D_grid, occupancy_grid, marching_cubes, vertex_normals, clean_mesh, extract_mesh,
+                 vertex_rays, vertex_colours, write_ply)
   evaluation     the trainer's validation metrics on the device (calculate_segmentation_metrics, calculate_depth_metrics, FrameEvaluator)
   optim          the trainers' optimizer.step(): Adam as one launch of the library (optim.Adam)
   draws          the training step's random variates drawn in the kernels (DrawState; opt-in)

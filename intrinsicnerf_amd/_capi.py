@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40021          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40022          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -240,6 +240,12 @@ SYMBOLS = {
     "inerf_vertex_rays": (_I, [_P, _L, _P, _L, _L, _I, C.c_float, C.c_float, C.c_float, _P, _P]),
     "inerf_vertex_rays_host": (_I, [_P, _L, _P, _L, _L, _I, C.c_float, C.c_float, C.c_float, _P]),
     "inerf_vertex_colours": (_I, [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P]),
+    "inerf_mc_workspace_bytes": (_L, [_I, _I, _I]),
+    "inerf_mc_count": (_I, [_P, _I, _I, _I, C.c_float, _P, _L, _P, _P]),
+    "inerf_mc_emit": (_I, [_P, _I, _I, _I, C.c_float, _P, _L, C.POINTER(C.c_double), _L, _L, _P, _P, _P, _P]),
+    "inerf_mesh_workspace_bytes": (_L, [_L, _L]),
+    "inerf_mesh_normals": (_I, [_P, _L, _P, _L, _P, _L, _P, _P]),
+    "inerf_mesh_clean": (_I, [_P, _L, _L, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "inerf_sem_maps": (_I, [_P, _L, _L, _I, _P, _L, _P, _L, _P]),
     "inerf_eval_workspace_bytes": (_L, [_L]),
     "inerf_eval_accumulate": (_I, [C.POINTER(EvalArgs), _P]),

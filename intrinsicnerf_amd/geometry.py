@@ -8,8 +8,13 @@ Mirrors, with the reference's names, arguments and returned tensors (citations r
                                        ``inerf_vertex_rays``
   vertex_colours                       extract_colour_mesh.py:27-41, 232-257 (the rays, the chunk loop over render_rays, to8b or
                                        valid_colour_map[label]) - three bytes per vertex reach the host, once
-Marching cubes and the mesh cleaning stay with the caller (``skimage.measure.marching_cubes`` on the returned array, ``open3d``).  See
-INTEGRATION.md.
+  marching_cubes, lattice_to_scene     extract_colour_mesh.py:186-201 (skimage.measure.marching_cubes, /(dim - 1), -0.5, x2, x extents / 2,
+                                       transform) - ``inerf_mc_count`` + ``inerf_mc_emit``: welded vertices, fp64 scene coordinates, int32 faces
+  vertex_normals                       open3d's compute_vertex_normals (open3d_utils.trimesh_to_open3d) - ``inerf_mesh_normals``
+  clean_mesh                           open3d_utils.clean_mesh, :214 - ``inerf_mesh_clean``
+  extract_mesh                         :149-219 chained on the device: two host reads of a few counters, nothing else leaves it
+  write_ply                            o3d.io.write_triangle_mesh, :263-266 - binary little-endian PLY, numpy on the host
+The triangulation is this project's own (csrc/mc_tables.h), not skimage's: DESIGN.md section 3, INTEGRATION.md.
 """
 import numpy as np
 import torch
@@ -17,7 +22,8 @@ import torch
 from . import _capi, kernels, layered, packing
 from .object_level import Embedder
 
-__all__ = ["grid_within_bound", "make_3D_grid", "occupancy_grid", "occupancy_activation", "vertex_rays", "vertex_colours"]
+__all__ = ["grid_within_bound", "make_3D_grid", "occupancy_grid", "occupancy_activation", "vertex_rays", "vertex_colours",
+           "marching_cubes", "lattice_to_scene", "vertex_normals", "clean_mesh", "extract_mesh", "write_ply"]
 
 STATUS_POINTS = 1 << 20        # lattice points per f16 range word of the fused launch - and per launch of the other paths
 VERTEX_CHUNK = 1 << 16         # vertices per render_rays call of vertex_colours
@@ -252,3 +258,109 @@ def vertex_colours(render_rays, vertices, normals, *, near=0.1, far=10.0, near_t
                                    labels=None if labels is None else labels[first:first + count])
         colours = colours.cpu().numpy()
         return (colours, labels.cpu().numpy()) if return_labels else colours
+
+
+def lattice_to_scene(dims, extents, transform):
+    """The fp64 3 x 4 map (numpy) from lattice coordinates to scene coordinates of extract_colour_mesh.py:190-201 composed into one:
+    ``/ (dim - 1)``, ``- 0.5``, ``x 2``, ``x extents / 2``, then ``transform`` (box to scene, [4, 4] or its first three rows).
+    ``dims``: the lattice's points per axis, one number or three."""
+    d = np.broadcast_to(np.asarray(dims, np.float64).reshape(-1), (3,))
+    if (d < 2).any():
+        raise ValueError(f"dims = {dims}: at least two lattice points per axis")
+    e = np.broadcast_to(np.asarray(extents, np.float64).reshape(-1), (3,))
+    t = np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, np.float64)
+    if t.ndim != 2 or t.shape[0] < 3 or t.shape[1] != 4:
+        raise ValueError(f"transform has shape {t.shape}, expected [4, 4] (or its first three rows)")
+    scale = 2.0 / (d - 1.0) * (e / 2.0)                  # x -> (x / (dim - 1) - 0.5) * 2 * extents / 2 = x * scale - extents / 2
+    out = np.empty((3, 4), np.float64)
+    out[:, :3] = t[:3, :3] * scale[None, :]
+    out[:, 3] = t[:3, :3] @ (-e / 2.0) + t[:3, 3]
+    return out
+
+
+def marching_cubes(occ, level, affine=None):
+    """``(vertices_lattice float32 [V, 3], vertices_scene float64 [V, 3] | None, faces int32 [F, 3])`` of the isosurface ``occ == level``
+    of a device lattice [nx, ny, nz], on the device.  Vertices lie on the lattice edges whose ends differ in ``occ > level``, in the
+    order owner lattice point, then axis (``index + (level - v0) / (v1 - v0)`` in fp32); faces wind so that their normals point
+    towards lower values.  ``affine``: a 3 x 4 fp64 map (``lattice_to_scene``) for the scene coordinates.  One host read of three
+    counters sizes the outputs; a lattice with a NaN or an infinity raises."""
+    with torch.no_grad():
+        workspace, totals = kernels.mc_count(occ, level)
+        nv, nt, bad = (int(x) for x in totals.cpu().tolist())                                        # the one host sync
+        if bad:
+            raise ValueError(f"marching_cubes: the lattice holds {bad} non-finite values")
+        a = None if affine is None else np.asarray(affine, np.float64)[:3].reshape(-1).tolist()
+        return kernels.mc_emit(occ, level, workspace, nv, nt, a)
+
+
+def vertex_normals(vertices, faces):
+    """float64 [V, 3] area-weighted vertex normals (open3d's compute_vertex_normals as far as it is known without it: DESIGN.md section 3)
+    of a device mesh: the fp64 sum of the incident triangles' cross products in ascending triangle index, normalised; a zero sum stays
+    zero.  ``vertices``: float32 or float64 [V, 3]; ``faces``: int32 [F, 3]."""
+    with torch.no_grad():
+        return kernels.mesh_normals(vertices.double() if isinstance(vertices, torch.Tensor) else vertices, faces)
+
+
+def clean_mesh(vertices, faces, normals=None, vertices_lattice=None, min_num_cluster=400, keep_single_cluster=False, return_counts=False):
+    """open3d_utils.clean_mesh on the device: ``(vertices, faces, normals, vertices_lattice)`` without the connected components of fewer
+    than ``min_num_cluster`` triangles (``keep_single_cluster``: without all but the largest) and without the vertices nothing
+    references any more, order kept, faces re-indexed.  ``vertices`` / ``normals``: float64 [V, 3] (normals may be None),
+    ``vertices_lattice``: float32 [V, 3] or None.  One host read of four counters; ``return_counts`` appends them as a dict."""
+    with torch.no_grad():
+        v = vertices.double()
+        f_out, l_out, v_out, n_out, totals = kernels.mesh_clean(faces, v.shape[0], min_num_cluster, keep_single_cluster, rows_f32=vertices_lattice,
+                                                                rows_f64_a=v, rows_f64_b=None if normals is None else normals.double())
+        nv, nt, comps, kept = (int(x) for x in totals.cpu().tolist())                                  # the one host sync
+        out = (v_out[:nv], f_out[:nt], None if n_out is None else n_out[:nv], None if l_out is None else l_out[:nv])
+        return out + ({"vertices": nv, "triangles": nt, "components": comps, "kept_components": kept},) if return_counts else out
+
+
+def extract_mesh(net, embed_fn, extents, transform, grid_dim, distances, level, occ_range=(-1., 1.), min_num_cluster=400,
+                 keep_single_cluster=False, embeddirs_fn=None):
+    """extract_colour_mesh.py:149-219 on the device: ``occupancy_grid``, ``marching_cubes`` with ``lattice_to_scene``, ``vertex_normals``
+    and ``clean_mesh``.  Returns ``(vertices float64 [V, 3] in scene coordinates, faces int32 [F, 3], normals float64 [V, 3])``, device
+    tensors.  Two host reads of a few counters (marching cubes' totals, the cleaning's), plus the grid's range words."""
+    occ = occupancy_grid(net, embed_fn, occ_range, extents, transform, grid_dim, distances, embeddirs_fn=embeddirs_fn)
+    _, scene, faces = marching_cubes(occ, level, lattice_to_scene(grid_dim, extents, transform))
+    normals = vertex_normals(scene, faces)
+    vertices, faces, normals, _ = clean_mesh(scene, faces, normals, min_num_cluster=min_num_cluster, keep_single_cluster=keep_single_cluster)
+    return vertices, faces, normals
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_ply(path, vertices, faces, colours=None, normals=None):
+    """Binary little-endian PLY: float64 x y z (as open3d writes them), optional float64 nx ny nz, optional uchar red green blue, then
+    ``uchar 3, int32 x 3`` per face.  Arrays may be numpy or tensors (device tensors are copied to the host here)."""
+    v = np.ascontiguousarray(_host(vertices), np.float64).reshape(-1, 3)
+    f = np.ascontiguousarray(_host(faces), np.int32).reshape(-1, 3)
+    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    header = ["ply", "format binary_little_endian 1.0", "comment intrinsicnerf_amd", f"element vertex {v.shape[0]}",
+              "property double x", "property double y", "property double z"]
+    if normals is not None:
+        n = np.ascontiguousarray(_host(normals), np.float64).reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"normals {n.shape} do not match vertices {v.shape}")
+        fields += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+        header += ["property double nx", "property double ny", "property double nz"]
+    if colours is not None:
+        c = np.ascontiguousarray(_host(colours)).reshape(-1, 3)
+        if c.dtype != np.uint8 or c.shape != v.shape:
+            raise ValueError(f"colours must be uint8 {v.shape}, got {c.dtype} {c.shape}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    rows = np.empty(v.shape[0], dtype=np.dtype(fields))
+    rows["x"], rows["y"], rows["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        rows["nx"], rows["ny"], rows["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colours is not None:
+        rows["red"], rows["green"], rows["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    tris = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    tris["n"], tris["v"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rows.tobytes())
+        fh.write(tris.tobytes())

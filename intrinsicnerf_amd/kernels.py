@@ -369,6 +369,96 @@ def vertex_colours(rgb=None, logits=None, colour_map=None, out=None, labels=None
     return out, labels
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# marching cubes and mesh cleaning (include/inerf.h, "Marching cubes and mesh cleaning"; csrc/mcubes.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def _mesh_tensor(t, name, dtype, cols=3):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a tensor on a HIP device (no CPU / eager fallback exists)")
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"{name} must be {dtype} [n, {cols}], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _workspace(nbytes, what, device):
+    if nbytes < 0:
+        _capi.check(int(nbytes), what)
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def mc_count(occ, level):
+    """``inerf_mc_count`` on a float32 device lattice [nx, ny, nz]: ``(workspace, totals)`` - the workspace ``mc_emit`` reads and the
+    int64 [3] device tensor {vertices, triangles, non-finite values}.  Nothing is read back here."""
+    if not isinstance(occ, torch.Tensor) or occ.dim() != 3:
+        raise ValueError("occ must be a [nx, ny, nz] tensor")
+    occ = _dev(occ, "occ")
+    nx, ny, nz = (int(s) for s in occ.shape)
+    workspace = _workspace(_capi.lib().inerf_mc_workspace_bytes(nx, ny, nz), "inerf_mc_workspace_bytes", occ.device)
+    totals = torch.empty(3, dtype=torch.int64, device=occ.device)
+    with torch.cuda.device(occ.device):
+        rc = _capi.lib().inerf_mc_count(_ptr(occ), nx, ny, nz, float(level), _ptr(workspace), workspace.numel(), _ptr(totals), _stream(occ))
+    _capi.check(rc, "inerf_mc_count")
+    return workspace, totals
+
+
+def mc_emit(occ, level, workspace, n_vertices, n_triangles, affine=None):
+    """``inerf_mc_emit`` after ``mc_count`` on the same lattice and level: ``(vertices_lattice float32 [V, 3], vertices_scene float64
+    [V, 3] or None, faces int32 [F, 3])`` on the device.  ``affine``: twelve numbers, the row-major 3 x 4 fp64 map to scene coordinates."""
+    occ = _dev(occ, "occ")
+    nx, ny, nz = (int(s) for s in occ.shape)
+    nv, nt = int(n_vertices), int(n_triangles)
+    lattice = torch.empty(nv, 3, dtype=torch.float32, device=occ.device)
+    scene = torch.empty(nv, 3, dtype=torch.float64, device=occ.device) if affine is not None else None
+    faces = torch.empty(nt, 3, dtype=torch.int32, device=occ.device)
+    a = None
+    if affine is not None:
+        flat = [float(x) for x in affine]
+        if len(flat) != 12:
+            raise ValueError(f"affine holds {len(flat)} numbers, expected the 12 of a 3 x 4 map")
+        a = (C.c_double * 12)(*flat)
+    with torch.cuda.device(occ.device):
+        rc = _capi.lib().inerf_mc_emit(_ptr(occ), nx, ny, nz, float(level), _ptr(workspace), workspace.numel(), a, nv, nt, _ptr(lattice),
+                                       _ptr(scene), _ptr(faces), _stream(occ))
+    _capi.check(rc, "inerf_mc_emit")
+    return lattice, scene, faces
+
+
+def mesh_normals(vertices, faces):
+    """float64 [V, 3] vertex normals of ``inerf_mesh_normals`` (vertices float64 [V, 3], faces int32 [F, 3], both on the device)."""
+    v = _mesh_tensor(vertices, "vertices", torch.float64)
+    f = _mesh_tensor(faces, "faces", torch.int32)
+    nv, nt = int(v.shape[0]), int(f.shape[0])
+    out = torch.empty(nv, 3, dtype=torch.float64, device=v.device)
+    workspace = _workspace(_capi.lib().inerf_mesh_workspace_bytes(nv, nt), "inerf_mesh_workspace_bytes", v.device)
+    with torch.cuda.device(v.device):
+        rc = _capi.lib().inerf_mesh_normals(_ptr(v), nv, _ptr(f), nt, _ptr(workspace), workspace.numel(), _ptr(out), _stream(v))
+    _capi.check(rc, "inerf_mesh_normals")
+    return out
+
+
+def mesh_clean(faces, n_vertices, min_triangles, keep_single_cluster=False, rows_f32=None, rows_f64_a=None, rows_f64_b=None):
+    """``inerf_mesh_clean``: ``(faces_out, out_f32, out_f64_a, out_f64_b, totals)`` - outputs sized for the input counts (the caller slices
+    them by ``totals``, the int64 [4] device tensor {vertices kept, triangles kept, components, components kept})."""
+    f = _mesh_tensor(faces, "faces", torch.int32)
+    nv, nt = int(n_vertices), int(f.shape[0])
+    rows = []
+    for name, t, dtype in (("rows_f32", rows_f32, torch.float32), ("rows_f64_a", rows_f64_a, torch.float64), ("rows_f64_b", rows_f64_b, torch.float64)):
+        t = None if t is None else _mesh_tensor(t, name, dtype)
+        if t is not None and (t.shape[0] != nv or t.device != f.device):
+            raise ValueError(f"{name} has {t.shape[0]} rows on {t.device}, expected {nv} on {f.device}")
+        rows.append(t)
+    outs = [None if t is None else torch.empty_like(t) for t in rows]
+    faces_out = torch.empty_like(f)
+    totals = torch.empty(4, dtype=torch.int64, device=f.device)
+    workspace = _workspace(_capi.lib().inerf_mesh_workspace_bytes(nv, nt), "inerf_mesh_workspace_bytes", f.device)
+    with torch.cuda.device(f.device):
+        rc = _capi.lib().inerf_mesh_clean(_ptr(f), nv, nt, int(min_triangles), int(bool(keep_single_cluster)), _ptr(rows[0]), _ptr(rows[1]),
+                                          _ptr(rows[2]), _ptr(workspace), workspace.numel(), _ptr(faces_out), _ptr(outs[0]), _ptr(outs[1]),
+                                          _ptr(outs[2]), _ptr(totals), _stream(f))
+    _capi.check(rc, "inerf_mesh_clean")
+    return faces_out, outs[0], outs[1], outs[2], totals
+
+
 def frame_to_u8(values):
     """``(255 * clip(x, 0, 1)).astype(uint8)`` (to8b, run_nerf_helpers.py:13) on the device; same shape, dtype uint8."""
     values = _dev(values, "values")

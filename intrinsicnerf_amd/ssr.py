@@ -414,6 +414,22 @@ class SSRRenderMixin:
         finally:
             self.return_raw, self.check_numerics = saved
 
+    def extract_colour_mesh(self, extents, transform, grid_dim=256, level=0.45, near_t=2.0, sem=False, colour_map=None, save_path=None,
+                            min_num_cluster=400, keep_single_cluster=False, occ_range=(-1., 1.)):
+        """extract_colour_mesh.py:149-266 in one call: the occupancy of the fine network on the lattice of the oriented bounding box,
+        marching cubes at ``level`` (0.45 as :134), scene coordinates, vertex normals, ``clean_mesh`` (geometry.extract_mesh: all on the
+        device), then ``vertex_colours`` and, with ``save_path``, the coloured PLY (geometry.write_ply).  Returns ``(vertices float64
+        [V, 3], faces int32 [F, 3], normals float64 [V, 3]`` - device tensors - ``, colours uint8 [V, 3]`` - numpy``)``."""
+        from . import geometry
+        vertices, faces, normals = geometry.extract_mesh(self.ssr_net_fine, self.embed_fn, extents, transform, grid_dim,
+                                                         (self.far - self.near) / self.N_importance, level, occ_range=occ_range,
+                                                         min_num_cluster=min_num_cluster, keep_single_cluster=keep_single_cluster,
+                                                         embeddirs_fn=self.embeddirs_fn)
+        colours = self.vertex_colours(vertices, normals, near_t=near_t, sem=sem, colour_map=colour_map)
+        if save_path is not None:
+            geometry.write_ply(save_path, vertices, faces, colours=colours, normals=normals)
+        return vertices, faces, normals, colours
+
     def _coalesced(self, flat_rays):
         """``self.chunk``, or the larger number of rays per ``volumetric_rendering`` call that gives the same frame
         (kernels.coalesced_chunk; results are bit-identical for any chunking): only when no random number is drawn per chunk (eval
