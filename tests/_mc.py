@@ -4,6 +4,8 @@
                               lattice point (linear index), then axis, and the vertex id of every (point, axis)
   faces(occ, level)           the case table (scripts/gen_mc_tables.py, imported - not the C header) applied cube by cube
   analytic fields, edge bookkeeping (directed edge multiplicities, Euler characteristic), enclosed volume, the shared-edge triangle graph
+  the seeded lattices of the boundary tests (tile_field, big_field, ...), the vertex graph (vertex_components) and the cleaning contract
+  on it (clean_reference(graph="vertex")), mesh_facts, and small meshes no marching cubes made (fan, strip, hub, bow_tie, ...)
 """
 import importlib.util
 import os
@@ -30,8 +32,8 @@ def inside(occ, level):
         return occ > np.float32(level)
 
 
-def vertices(occ, level):
-    """(float32 [V, 3], int64 [nx, ny, nz, 3] vertex id or -1)"""
+def crossings(occ, level):
+    """(bool [nx, ny, nz, 3]: the owned edge towards +axis straddles the level, float32 [nx, ny, nz, 3]: its t = (level - v0) / (v1 - v0))"""
     occ = np.asarray(occ, np.float32)
     level = np.float32(level)
     ins = inside(occ, level)
@@ -46,7 +48,13 @@ def vertices(occ, level):
         flag[lo + (axis,)] = ins[lo] != ins[hi]
         with np.errstate(all="ignore"):
             t[lo + (axis,)] = (level - occ[lo]) / (occ[hi] - occ[lo])            # float32 throughout
-    ids = np.full(shape + (3,), -1, np.int64)
+    return flag, t
+
+
+def vertices(occ, level):
+    """(float32 [V, 3], int64 [nx, ny, nz, 3] vertex id or -1)"""
+    flag, t = crossings(occ, level)
+    ids = np.full(flag.shape, -1, np.int64)
     ids[flag] = np.arange(int(flag.sum()))                                       # C order: point linear index, then axis
     idx = np.argwhere(flag)                                                      # same order
     verts = idx[:, :3].astype(np.float32)
@@ -99,9 +107,66 @@ def torus_field(shape, centre, major, minor):
     return (minor - np.sqrt(q ** 2 + p[..., 2] ** 2)).astype(np.float32)
 
 
+def noise_field(seed, shape):
+    return np.random.default_rng(seed).uniform(0, 1, shape).astype(np.float32)
+
+
+# The lattices of tests/test_mcubes_edges_gpu.py; tests/test_mc_reference_cpu.py holds what each is chosen for and checks it.
+TILE_SHAPE = (9, 17, 67)                                 # three ragged classify tiles (4 x 8 x 32 lattice points) along every axis
+BIG_SHAPE = (40, 40, 70)
+
+
+def tile_field():
+    return noise_field(1, TILE_SHAPE)
+
+
+def big_field():
+    return noise_field(8, BIG_SHAPE)
+
+
+def sparse_field():
+    return noise_field(4, (13, 19, 41)) ** 3
+
+
+def integer_field():
+    return np.random.default_rng(5).integers(0, 4, (9, 17, 35)).astype(np.float32)
+
+
+def binary_field():
+    return (np.random.default_rng(6).uniform(0, 1, (9, 17, 35)) > 0.7).astype(np.float32)
+
+
+def scale_base():
+    return noise_field(2, (7, 11, 37)) - np.float32(0.5)
+
+
+def scaled(occ, exponent):
+    """occ * 2^exponent, rounded once to float32 (exact unless the result is denormal)"""
+    return np.ldexp(np.asarray(occ, np.float64), exponent).astype(np.float32)
+
+
+def tile_face_crossings(occ, level, tile=(4, 8, 32)):
+    """per axis: the straddling edges whose owner is the last point of a classify tile along that axis - its far end is a halo value"""
+    flag, _ = crossings(occ, level)
+    index = np.meshgrid(*[np.arange(n) for n in flag.shape[:3]], indexing="ij")
+    return [int(flag[..., axis][index[axis] % tile[axis] == tile[axis] - 1].sum()) for axis in range(3)]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # mesh bookkeeping
 # ---------------------------------------------------------------------------------------------------------------------
+def mesh_facts(v, f):
+    """what the boundary tests rely on, of a mesh (vertices [V, 3], faces [F, 3]): V, F, the shared-edge components (scipy's result and
+    their sizes in ascending order), whether the vertex graph splits the triangles the same way, the largest valence, the number of
+    zero-area triangles"""
+    f = np.asarray(f, np.int64)
+    components = edge_components(f)
+    by_vertex = vertex_components(f, len(v))[1][f[:, 0]]
+    return {"V": len(v), "F": len(f), "components": components, "sizes": np.sort(np.bincount(components[1])),
+            "partitions_equal": same_partition(components[1], by_vertex), "max_valence": int(valence(f, len(v)).max()),
+            "zero_area": int(zero_area(v, f).sum())}
+
+
 def directed_edges(f):
     f = np.asarray(f, np.int64)
     return np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], 0)
@@ -139,7 +204,7 @@ def edge_components(f):
     d = directed_edges(f)
     und = np.sort(d, axis=1)
     tri = np.tile(np.arange(len(f)), 3)
-    _, inv = np.unique(und, axis=0, return_inverse=True)
+    _, inv = np.unique(und[:, 0] * (int(und.max(initial=0)) + 1) + und[:, 1], return_inverse=True)      # one int64 key per undirected edge
     inv = inv.reshape(-1)
     order = np.argsort(inv, kind="stable")
     inv_s, tri_s = inv[order], tri[order]
@@ -148,22 +213,122 @@ def edge_components(f):
     return connected_components(g, directed=False)
 
 
-def clean_reference(f, n_vertices, min_triangles, keep_single):
-    """(kept triangle mask, kept vertex mask, re-indexed faces) by the shared-edge components"""
-    f = np.asarray(f, np.int64)
-    n, label = edge_components(f)
-    sizes = np.bincount(label, minlength=n)
-    if keep_single:
-        first_vertex = np.full(n, n_vertices, np.int64)
-        np.minimum.at(first_vertex, label, f.min(1))
-        best = sorted(range(n), key=lambda c: (-sizes[c], first_vertex[c]))[0]
-        keep_t = label == best
+def vertex_components(f, n_vertices):
+    """(number of components, label per vertex) of the graph whose nodes are the n_vertices vertices and whose links are triangle
+    sides; a face with an index outside [0, n_vertices) is ignored, a vertex no face names is a component of its own"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    f = np.asarray(f, np.int64).reshape(-1, 3)
+    f = f[((f >= 0) & (f < n_vertices)).all(1)]
+    d = directed_edges(f)
+    g = coo_matrix((np.ones(len(d)), (d[:, 0], d[:, 1])), shape=(n_vertices, n_vertices))
+    return connected_components(g, directed=False)
+
+
+def same_partition(a, b):
+    """two label arrays split their items into the same groups"""
+    a, b = np.asarray(a), np.asarray(b)
+    pairs = np.unique(np.stack([a, b], 1), axis=0)
+    return a.shape == b.shape and len(pairs) == len(np.unique(a)) == len(np.unique(b))
+
+
+def clean_reference(f, n_vertices, min_triangles, keep_single, graph="edge", components=None):
+    """(kept triangle mask, kept vertex mask, re-indexed faces, triangles per component).
+
+    graph="edge": by the shared-edge components (``components``: a result of edge_components(f) computed earlier).
+    graph="vertex": the contract of inerf_mesh_clean - components of the vertex graph, each labelled by its smallest vertex index,
+    its triangles counted by their first vertex; keep_single keeps the component with the most triangles, a tie going to the lowest
+    label; faces with an index outside [0, n_vertices) are dropped, and so are the vertices no kept triangle names.  The sizes are
+    those of the components that own a triangle, in ascending label."""
+    f = np.asarray(f, np.int64).reshape(-1, 3)
+    if graph == "vertex":
+        valid = ((f >= 0) & (f < n_vertices)).all(1)
+        _, comp = vertex_components(f, n_vertices)
+        smallest = np.full(comp.max() + 1 if n_vertices else 0, n_vertices, np.int64)
+        np.minimum.at(smallest, comp, np.arange(n_vertices))
+        label = smallest[comp]                                                  # per vertex: the smallest index of its component
+        tri_label = np.where(valid, label[np.where(valid, f[:, 0], 0)], -1)
+        count = np.bincount(tri_label[valid], minlength=n_vertices)             # per label
+        if keep_single:
+            best = min(np.flatnonzero(count > 0), key=lambda c: (-count[c], c)) if valid.any() else -2
+            keep_t = tri_label == best
+        else:
+            keep_t = valid & (count[np.where(valid, tri_label, 0)] >= min_triangles)
+        sizes = count[count > 0]
+    elif graph == "edge":
+        n, label = edge_components(f) if components is None else components
+        sizes = np.bincount(label, minlength=n)
+        if keep_single:
+            first_vertex = np.full(n, n_vertices, np.int64)
+            np.minimum.at(first_vertex, label, f.min(1))
+            best = sorted(range(n), key=lambda c: (-sizes[c], first_vertex[c]))[0]
+            keep_t = label == best
+        else:
+            keep_t = sizes[label] >= min_triangles
     else:
-        keep_t = sizes[label] >= min_triangles
+        raise ValueError(graph)
     keep_v = np.zeros(n_vertices, bool)
     keep_v[f[keep_t].reshape(-1)] = True
     new = np.cumsum(keep_v) - 1
     return keep_t, keep_v, new[f[keep_t]].astype(np.int32), sizes
+
+
+def valence(f, n_vertices):
+    """triangles that name each vertex (a triangle that names it twice counts twice, as the kernels' slots do)"""
+    return np.bincount(np.asarray(f, np.int64).reshape(-1), minlength=n_vertices)
+
+
+def zero_area(v, f):
+    """bool per triangle: the fp64 cross product (b - a) x (c - a) is the zero vector"""
+    v = np.asarray(v, np.float64)
+    f = np.asarray(f, np.int64)
+    return ~np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]).any(1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# small meshes from elsewhere: (int32 faces [F, 3], number of vertices)
+# ---------------------------------------------------------------------------------------------------------------------
+def fan(n):
+    """n triangles about vertex 0 (a closed umbrella over the rim 1 .. n)"""
+    return np.array([[0, 1 + t, 1 + (t + 1) % n] for t in range(n)], np.int32), n + 1
+
+
+def strip(n, descending=False):
+    """a strip of n triangles (t, t + 1, t + 2) over n + 2 vertices; descending: vertex v renamed n + 1 - v, so that indices fall
+    along the strip and every union hooks the vertex met earlier under the one met later"""
+    f = np.arange(n, dtype=np.int64)[:, None] + np.arange(3)
+    if descending:
+        f = n + 1 - f
+    return f.astype(np.int32), n + 2
+
+
+def relabel(f, n_vertices, rng):
+    """the same mesh with its vertices renamed by a random permutation and its triangles in a random order"""
+    perm = rng.permutation(n_vertices)
+    return perm[np.asarray(f, np.int64)][rng.permutation(len(f))].astype(np.int32)
+
+
+def hub(n):
+    """n triangles that share nothing but the LAST vertex (2 n), which takes each of the three positions in turn"""
+    t = np.arange(n, dtype=np.int64)
+    f = np.stack([np.full(n, 2 * n), 2 * t, 2 * t + 1], 1)
+    cols = (np.arange(3)[None, :] - (t % 3)[:, None]) % 3                       # row t rolled by t % 3: a cyclic shift keeps the winding
+    return np.take_along_axis(f, cols, 1).astype(np.int32), 2 * n + 1
+
+
+def bow_tie():
+    """two triangles that share one vertex and no edge"""
+    return np.array([[0, 1, 2], [2, 3, 4]], np.int32), 5
+
+
+def disjoint_triangles(n):
+    return np.arange(3 * n, dtype=np.int32).reshape(n, 3), 3 * n
+
+
+def two_equal_strips(n):
+    """two strips of n triangles each; the one whose triangles come SECOND holds vertex 0, so the lowest label is not the first met"""
+    a, nv = strip(n)
+    return np.concatenate([a + nv, a]).astype(np.int32), 2 * nv
 
 
 def normals_reference(v, f):
