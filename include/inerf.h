@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40022
+#define INERF_ABI_VERSION 40023
 
 /* error codes */
 #define INERF_OK              0
@@ -1232,6 +1232,84 @@ typedef struct inerf_eval_args {
 } inerf_eval_args;
 int64_t inerf_eval_workspace_bytes(int64_t n);
 int inerf_eval_accumulate(const inerf_eval_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Intrinsic-image quality metrics (csrc/imq.hip): the sums behind mse / psnr, scale-invariant MSE, LMSE and SSIM / DSSIM of a stack
+ * of image pairs.  Neither reference code base has code for these; the definitions below are the contract.
+ *   pred, trgt: fp32 [H, W, C], C = 1 or 3.  mask: fp32 [H, W], optional; a pixel is valid iff its mask value > 0 (NaN: invalid);
+ *   without a mask every pixel is valid.  M = the number of valid pixels.  Sums run over valid pixels and all channels; products and
+ *   sums are fp64 from the fp32 inputs.
+ *   mse    = S(g-p)^2 / (C M),  psnr = -10 log10 mse.
+ *   si_mse (Grosse et al. 2009 ssq_error; one scale per image, shared by the channels): Spp = S p^2, Spg = S p g, Sgg = S g^2,
+ *            a = Spg / Spp if Spp > 1e-5 else 0,  si_mse = S(g - a p)^2 / (C M) = (Sgg - 2 a Spg + a^2 Spp) / (C M).
+ *   lmse   (Grosse et al. local_error): k x k windows, k = window_size, at origins i in range(0, H-k+1, s), j in range(0, W-k+1, s),
+ *            s = window_shift; each window has its own a_w (same rule, same threshold, over the window's valid pixels);
+ *            lmse = sum_w (Sgg_w - 2 a_w Spg_w + a_w^2 Spp_w) / sum_w Sgg_w.  No window or a zero denominator: 0 / 0 = NaN.
+ *            1 <= s <= k, k % s == 0 and k / s <= 8, else INERF_E_UNSUPPORTED.
+ *   ssim   (Wang et al. 2004, as skimage structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=1,
+ *            channel_axis=-1)): 11 taps w_i ~ exp(-(i / 1.5)^2 / 2), i = -5..5, normalised in fp64 BY THE CALLER (taps[11]; the
+ *            device evaluates no exp); per channel over the (H-10) x (W-10) valid region, no padding: mu_x, mu_y, E[x^2], E[y^2],
+ *            E[xy] filtered, sigma^2 and sigma_xy by subtraction,
+ *            map = (2 mu_x mu_y + c1)(2 sigma_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(sigma_x^2 + sigma_y^2 + c2)),  c1 = 1e-4, c2 = 9e-4;
+ *            ssim = the mean of map over the channels and the positions whose CENTRE pixel is valid (the mask selects positions, it
+ *            does not alter what is filtered);  dssim = (1 - ssim) / 2.  H < 11 or W < 11: no position, NaN.
+ *   A NaN input propagates to every metric it enters, as in numpy.
+ * The host finishing is a few float64 lines on these ten numbers (intrinsicnerf_amd/evaluation.py, finish_image_quality).
+ * ------------------------------------------------------------------------------------------- */
+/* sums[n_images, INERF_IMQ_SUMS] (double), per image */
+#define INERF_IMQ_SUMS 7
+#define INERF_IMQ_SPP       0   /* S p^2                                              */
+#define INERF_IMQ_SPG       1   /* S p g                                              */
+#define INERF_IMQ_SGG       2   /* S g^2                                              */
+#define INERF_IMQ_SQ_DIFF   3   /* S (g - p)^2                                        */
+#define INERF_IMQ_LMSE_NUM  4   /* sum over windows of S_w (g - a_w p)^2              */
+#define INERF_IMQ_LMSE_DEN  5   /* sum over windows of S_w g^2                        */
+#define INERF_IMQ_SSIM_SUM  6   /* sum of the SSIM map over channels and positions    */
+/* counts[n_images, INERF_IMQ_COUNTS] (int64), per image */
+#define INERF_IMQ_COUNTS 3
+#define INERF_IMQ_N_VALID   0   /* M: valid pixels (not times C)                      */
+#define INERF_IMQ_N_WINDOWS 1   /* LMSE windows                                       */
+#define INERF_IMQ_N_SSIM    2   /* SSIM positions with a valid centre (not times C)   */
+
+/* One call for n_images pairs; sums and counts are WRITTEN, not added.  Image i of an input starts i * image_stride floats after
+ * the pointer; its pixel (y, x) lies (y * width + x) * pixel_stride floats further and holds `channels` consecutive floats (the
+ * mask: one) - so a column range of a frame pack goes in as it is.
+ * Four launches: cell moments (the image cut into s x s cells, every pixel read once), windows (each a sum of (k / s)^2 cells),
+ * the LDS-tiled separable 11-tap stencil with its halo in LDS, and a one-workgroup-per-image launch that adds the stages' partial
+ * rows in index order.  Bit-identical from run to run: no floating-point atomic, fixed fp64 trees into one plain-stored row per
+ * workgroup in `workspace` (inerf_image_quality_workspace_bytes(...) bytes, else INERF_E_WORKSPACE); no kernel waits on another
+ * workgroup; the grids depend on the shapes alone; nothing is allocated or synchronised; capturable into a HIP graph.
+ * INERF_E_INVALID: a NULL args / pred / trgt / sums / counts, a negative size or image stride, a pixel stride smaller than its width
+ * (channels; 1 for the mask), a misaligned pointer (4 bytes for floats, 8 for sums / counts / workspace), channels not 1 or 3.
+ * INERF_E_UNSUPPORTED: the window rule above, n_images > 65535, height * width > 2^31 - 1.  n_images == 0 or height * width == 0 is
+ * a no-op.  inerf_image_quality_workspace_bytes returns the same error codes (negative) for the same arguments. */
+typedef struct inerf_imq_args {
+    int32_t n_images;
+    int32_t height;
+    int32_t width;
+    int32_t channels;
+    const float* pred;
+    int64_t pred_pixel_stride;
+    int64_t pred_image_stride;
+    const float* trgt;
+    int64_t trgt_pixel_stride;
+    int64_t trgt_image_stride;
+    const float* mask;               /* optional */
+    int64_t mask_pixel_stride;
+    int64_t mask_image_stride;
+    int32_t window_size;
+    int32_t window_shift;
+    double taps[11];
+    double c1;
+    double c2;
+    double* sums;                    /* [n_images, INERF_IMQ_SUMS]   */
+    int64_t* counts;                 /* [n_images, INERF_IMQ_COUNTS] */
+    void* workspace;
+    int64_t workspace_bytes;
+} inerf_imq_args;
+int64_t inerf_image_quality_workspace_bytes(int64_t n_images, int64_t height, int64_t width, int channels, int window_size,
+                                            int window_shift);
+int inerf_image_quality(const inerf_imq_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40022          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40023          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -141,6 +141,22 @@ EVAL_COUNTS, EVAL_SUMS = 8, 6
 EVAL_COUNT_NAMES = ("n_not_ignored", "n_pixels", "n_pred_positive", "n_mask", "r1", "r2", "r3", "n_rgb")
 EVAL_SUM_NAMES = ("abs_rel", "abs_diff", "sq_rel", "sq_diff", "sq_log_diff", "rgb_sq")
 
+
+
+class ImqArgs(C.Structure):
+    """inerf_imq_args: one image-quality call over a stack of image pairs (include/inerf.h, inerf_image_quality)."""
+    _fields_ = [("n_images", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("pred", C.c_void_p), ("pred_pixel_stride", C.c_int64), ("pred_image_stride", C.c_int64),
+                ("trgt", C.c_void_p), ("trgt_pixel_stride", C.c_int64), ("trgt_image_stride", C.c_int64),
+                ("mask", C.c_void_p), ("mask_pixel_stride", C.c_int64), ("mask_image_stride", C.c_int64),
+                ("window_size", C.c_int32), ("window_shift", C.c_int32), ("taps", C.c_double * 11), ("c1", C.c_double), ("c2", C.c_double),
+                ("sums", C.c_void_p), ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+IMQ_SUMS, IMQ_COUNTS = 7, 3
+IMQ_SUM_NAMES = ("spp", "spg", "sgg", "sq_diff", "lmse_num", "lmse_den", "ssim_sum")
+IMQ_COUNT_NAMES = ("n_valid", "n_windows", "n_ssim")
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -249,6 +265,8 @@ SYMBOLS = {
     "inerf_sem_maps": (_I, [_P, _L, _L, _I, _P, _L, _P, _L, _P]),
     "inerf_eval_workspace_bytes": (_L, [_L]),
     "inerf_eval_accumulate": (_I, [C.POINTER(EvalArgs), _P]),
+    "inerf_image_quality_workspace_bytes": (_L, [_L, _L, _L, _I, _I, _I]),
+    "inerf_image_quality": (_I, [C.POINTER(ImqArgs), _P]),
 }
 
 _lib = None

@@ -1898,3 +1898,105 @@ def eval_accumulate(counts, sums, n_classes, ignore_label=-1, logits=None, pred_
     del held
     _capi.check(rc, "inerf_eval_accumulate")
     return label, entropy
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# intrinsic-image quality metrics (csrc/imq.hip).  Inputs are VIEWS, never copied: an image is [H, W, C] or, with ``shape=(H, W)``,
+# its flat form [H * W, C] - either with a leading stack axis - with unit stride along the channels, one pixel stride and one image
+# stride: a column range of a frames.pack_maps pack, or a tensor of its own
+# ---------------------------------------------------------------------------------------------------------------------
+def _imq_view(t, name, shape, channels, n=None):
+    """``(tensor, n_images, height, width, pixel stride, image stride)`` of one input of ``image_quality``; ``channels`` None: the
+    mask (one float per pixel, no channel axis)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    dims, strides = list(t.shape), list(t.stride())
+    width = 1 if channels is None else channels
+    if channels is not None:
+        if not dims or dims[-1] != width:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected a last axis of {width}")
+        if width > 1 and strides[-1] != 1:
+            raise ValueError(f"{name} must have unit stride along its channels, got stride {strides[-1]}")
+        dims, strides = dims[:-1], strides[:-1]
+    if shape is not None:
+        h, w = int(shape[0]), int(shape[1])
+    elif len(dims) in (2, 3):
+        h, w = dims[-2], dims[-1]
+    else:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}: expected [H, W{', C' if channels else ''}] with an optional leading stack "
+                         "axis (or a flat form with shape=(H, W))")
+    if dims[-2:] == [h, w] and len(dims) in (2, 3):
+        if h > 1 and w > 1 and strides[-2] != w * strides[-1]:
+            raise ValueError(f"{name}: its rows are {strides[-2]} floats apart, expected width * pixel stride = {w * strides[-1]}")
+        pixel = strides[-1] if w > 1 else strides[-2]
+        lead = len(dims) - 2
+    elif dims[-1:] == [h * w] and len(dims) in (1, 2):
+        pixel = strides[-1]
+        lead = len(dims) - 1
+    else:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, which is not {h} x {w} pixels{f' of {channels}' if channels else ''}")
+    if h * w <= 1:
+        pixel = width
+    if pixel < width:
+        raise ValueError(f"{name} has a pixel stride of {pixel} floats, smaller than its width {width}")
+    count = dims[0] if lead else 1
+    image = strides[0] if lead and count > 1 else 0
+    if n is not None and count != n:
+        raise ValueError(f"{name} holds {count} images, expected {n}")
+    if image < 0:
+        raise ValueError(f"{name} has a negative image stride")
+    return t, count, h, w, int(pixel), int(image)
+
+
+def image_quality_workspace_bytes(n_images, height, width, channels, window_size=20, window_shift=10):
+    need = int(_capi.lib().inerf_image_quality_workspace_bytes(int(n_images), int(height), int(width), int(channels), int(window_size),
+                                                               int(window_shift)))
+    _capi.check(min(need, 0), "inerf_image_quality_workspace_bytes")
+    return need
+
+
+def image_quality(pred, target, mask=None, shape=None, window_size=20, window_shift=10, workspace=None):
+    """One ``inerf_image_quality`` call: ``(sums [N, 7] float64, counts [N, 3] int64)`` on the device for N pairs of fp32 images
+    (``_capi.IMQ_SUM_NAMES`` / ``IMQ_COUNT_NAMES``; finished on the host by ``evaluation.finish_image_quality``).  ``pred`` and
+    ``target``: [H, W, C] or [N, H, W, C], C = 1 or 3; with ``shape=(H, W)`` also [H * W, C] or [N, H * W, C] - e.g. columns of a
+    frame's pack.  ``mask`` (optional): the same without the channel axis; a pixel is valid iff its mask value > 0."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() < 2 or pred.shape[-1] not in (1, 3):
+        raise ValueError("pred must be a tensor whose last axis holds 1 or 3 channels")
+    c = int(pred.shape[-1])
+    pred, n, h, w, pp, pi = _imq_view(pred, "pred", shape, c)
+    target, _, _, _, tp, ti = _imq_view(target, "target", (h, w), c, n)
+    named = [("pred", pred), ("target", target)]
+    a = _capi.ImqArgs()
+    a.n_images, a.height, a.width, a.channels = n, h, w, c
+    a.pred, a.pred_pixel_stride, a.pred_image_stride = pred.data_ptr(), pp, pi
+    a.trgt, a.trgt_pixel_stride, a.trgt_image_stride = target.data_ptr(), tp, ti
+    a.mask_pixel_stride = 1
+    if mask is not None:
+        mask, _, _, _, mp, mi = _imq_view(mask, "mask", (h, w), None, n)
+        named.append(("mask", mask))
+        a.mask, a.mask_pixel_stride, a.mask_image_stride = mask.data_ptr(), mp, mi
+    if workspace is not None:
+        if not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.float64 and workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous float64 tensor")
+        named.append(("workspace", workspace))
+    device = _eval_devices(named)
+    a.window_size, a.window_shift = int(window_size), int(window_shift)
+    from .evaluation import ssim_taps
+    a.taps = (C.c_double * 11)(*ssim_taps())
+    a.c1, a.c2 = 1e-4, 9e-4
+    need = image_quality_workspace_bytes(n, h, w, c, window_size, window_shift)
+    if workspace is None:
+        workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=device)
+    sums = torch.empty(n, _capi.IMQ_SUMS, dtype=torch.float64, device=device)
+    counts = torch.empty(n, _capi.IMQ_COUNTS, dtype=torch.int64, device=device)
+    if n == 0 or h * w == 0:
+        sums.zero_()
+        counts.zero_()
+    a.sums, a.counts = sums.data_ptr(), counts.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_image_quality(C.byref(a), _stream(sums))
+    _capi.check(rc, "inerf_image_quality")
+    return sums, counts

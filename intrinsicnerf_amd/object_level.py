@@ -416,7 +416,7 @@ def to8b(x):
 
 
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0, update_cluster=False,
-                b_f=0.5, cluster_manager_factory=None, refresh=None):
+                b_f=0.5, cluster_manager_factory=None, refresh=None, evaluator=None):
     """Render every pose of ``render_poses`` - run_nerf.py:142-272; returns ``(rgbs, disps, cluster_manager)``.
 
     Same arguments, same returned stacks (``[N, H, W, 3]`` / ``[N, H, W]`` float32 numpy), same files in ``savedir``
@@ -427,7 +427,10 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     reference's ``Cluster_Manager.update_center`` (sklearn; training control plane, not rebuilt here): pass the
     reference's class as ``cluster_manager_factory``.  ``refresh`` (a ``refresh.ClusterRefresh``; opt-in): with
     ``update_cluster`` the sample set, the fit and the ``c*`` / ``edit*`` images stay on the device (csrc/refresh.hip) - same
-    returned values, same files; no ``cluster_manager_factory`` is needed then."""
+    returned values, same files; no ``cluster_manager_factory`` is needed then.  ``evaluator`` (an
+    ``evaluation.FrameEvaluator``; opt-in): when it holds targets registered for ``render_poses``, every frame's rgb, albedo and
+    shading columns are handed to its ``add_frame`` from the device pack, before the host copy - the reference has no metric code
+    here (its PSNR line is commented out, run_nerf.py:187-191) and ``gt_imgs`` stays unread; read ``evaluator.results()`` afterwards."""
     import os
     from . import frames
     H, W, focal = hwf
@@ -456,6 +459,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
                 frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), frames.to8b(img))
 
     on_device = bool(update_cluster) and refresh is not None
+    evaluating = evaluator is not None and evaluator.begin(render_poses)
     streamer, in_flight = None, []
     for i, c2w in enumerate(render_poses):
         out = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
@@ -467,6 +471,10 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
             if i == 0:                                   # class_num == 1 (run_nerf.py:218): the (acc > 10) label is not read
                 refresh.begin(len(render_poses), H, W, 1, pack.device)
             refresh.add_frame(i, pack, widths, keys)
+        if evaluating:
+            start = {k: sum(widths[:j]) for j, k in enumerate(keys)}
+            cols = {k: pack[:, start[k]:start[k] + widths[j]] for j, k in enumerate(keys)}
+            evaluator.add_frame(i, rgb=cols["rgb_map"], albedo=cols["albedo_map"], shading=cols["shading_map"])
         if pack.is_cuda:
             if streamer is None:
                 streamer = frames.FrameStreamer(pack.device)
