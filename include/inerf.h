@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40023
+#define INERF_ABI_VERSION 40024
 
 /* error codes */
 #define INERF_OK              0
@@ -1310,6 +1310,93 @@ typedef struct inerf_imq_args {
 int64_t inerf_image_quality_workspace_bytes(int64_t n_images, int64_t height, int64_t width, int channels, int window_size,
                                             int window_shift);
 int inerf_image_quality(const inerf_imq_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frame images (csrc/frame_vis.hip): every 8- and 16-bit image the render_path loops write or return, made from the packed frame
+ * frame[n, stride] (fp32, a pixel's maps side by side) in one launch - what the reference does on the host per frame: to8b
+ * (run_nerf.py:193-211 | trainer.py:1242, 1340-1343, 1379), astype(np.uint16) of disparity and of depth * 1000
+ * (trainer.py:1344-1345), the label map's astype(np.uint8) (trainer.py:1318), to8b(acc > 10) (run_nerf.py:173),
+ * valid_colour_map[label] (trainer.py:1269, 1294) and imgviz.depth2rgb of depth and entropy (trainer.py:1314, 1321), whose results
+ * the trainer stacks, writes as videos and logs (trainer.py:1089-1110, 1394).
+ * A PRODUCT reads `width` consecutive columns of the frame from `column` on and writes one plane of bytes, pixel after pixel.
+ * All arithmetic is fp32, each operation rounded on its own.  (int32)x below: truncation toward zero, and 0 for NaN or
+ * |x| >= 2^31 - what numpy's float32 -> uint16 / uint8 casts give (65535.9 -> 65535, 65536 -> 0, 70000 -> 4464, -1 -> 65535,
+ * -0.5 -> 0, NaN, +-inf, 3e9 -> 0).
+ *   kind      width   bytes / pixel   rule
+ *   TO8B      1 | 3   width           (uint8)(255 * clip(x, 0, 1)), NaN -> 0: byte-equal to inerf_frame_to_u8
+ *   U16       1       2, little-endian  the low 16 bits of (int32)(x * a); a = 1: disparity, a = 1000: depth in mm
+ *   U8_CAST   1       1               the low 8 bits of (int32)x
+ *   THRESH    1       1               x > a ? 255 : 0 (NaN -> 0) = to8b(float32(x > a))
+ *   PALETTE   1       3               l = x truncated toward zero; palette[l] (uint8 [n_colours, 3], device) if 0 <= l < n_colours,
+ *                                     else (0, 0, 0): NaN, +-inf and |x| >= 2^31 are black too (NOT palette[0], which the
+ *                                     (int32) rule's 0 would select), and so is every pixel when n_colours == 0
+ *   JET       1       3               t = (x - lo) / (hi - lo); NaN -> (0, 0, 0); else JET[min((int)(clamp(t, 0, 1) * 256), 255)].
+ *                                     (lo, hi) = (a, b), or - `range` non-NULL - a device float[2] the kernel reads (the map's
+ *                                     own range from inerf_frame_range: no host synchronisation).  hi == lo, +-inf and values
+ *                                     outside [lo, hi] have no special case: IEEE arithmetic and the rules above decide
+ * JET[256][3] = (matplotlib.colormaps['jet'](arange(256))[:, :3] * 255).round() (csrc/jet_table.h, generated by
+ * scripts/gen_jet_table.py; inerf_jet_table() returns its 768 bytes on the host).  With these rules a JET product equals
+ * (cmap(where(isnan(t), 0, t))[..., :3] * 255).round().astype(uint8) with black where t is NaN - imgviz.depth2rgb.
+ * ------------------------------------------------------------------------------------------- */
+#define INERF_FRAME_MAX_PRODUCTS 16
+#define INERF_FRAME_TO8B     0
+#define INERF_FRAME_U16      1
+#define INERF_FRAME_U8_CAST  2
+#define INERF_FRAME_THRESH   3
+#define INERF_FRAME_PALETTE  4
+#define INERF_FRAME_JET      5
+
+typedef struct inerf_frame_product {
+    int32_t kind;                    /* INERF_FRAME_* */
+    int32_t column;                  /* first column of the frame it reads */
+    int32_t width;                   /* columns it reads */
+    int32_t reserved;
+    float a;                         /* U16: scale; THRESH: threshold; JET: lo */
+    float b;                         /* JET: hi */
+    const float* range;              /* JET: device float[2] = (lo, hi) read by the kernel instead of (a, b); else NULL */
+    int64_t offset;                  /* of its plane in `out`, in bytes: written by inerf_frame_products_layout */
+} inerf_frame_product;
+
+typedef struct inerf_frame_products_args {
+    const float* frame;              /* [n, stride] fp32, device */
+    int64_t stride;                  /* floats between two pixels */
+    int64_t n;                       /* pixels */
+    int32_t n_products;              /* 0 .. INERF_FRAME_MAX_PRODUCTS */
+    int32_t n_colours;
+    const unsigned char* palette;    /* [n_colours, 3] uint8, device; read by PALETTE products only */
+    unsigned char* out;              /* the planes, device, 16-byte aligned */
+    int64_t out_bytes;
+    inerf_frame_product products[INERF_FRAME_MAX_PRODUCTS];
+} inerf_frame_products_args;
+
+/* Host only, no HIP call: writes products[k].offset - plane k holds n * (bytes / pixel) bytes, pixel after pixel, and starts at a
+ * multiple of 16 bytes after plane k - 1 - and returns the byte count `out` needs (0 for n == 0), or a negative error code:
+ * INERF_E_INVALID for NULL args, n < 0, n_products outside 0 .. 16, a kind that does not exist or a width its kind does not take. */
+int64_t inerf_frame_products_layout(inerf_frame_products_args* args);
+
+/* One launch for all products of one frame.  A workgroup stages the used columns of its 512 pixels in LDS, every column read from
+ * memory once however many products use it; a lane takes 4 consecutive pixels and writes whole dwords (4 bytes grey, 8 bytes
+ * 16-bit, 12 bytes RGB), the n mod 4 tail byte by byte; the jet table sits in LDS.  No atomics, no hand-off between workgroups,
+ * the grid depends on n alone; nothing is allocated, synchronised or read on the host: capturable into a HIP graph.
+ * Checked before any HIP call.  INERF_E_INVALID: what inerf_frame_products_layout refuses; offsets that are not the layout's;
+ * stride < 1, a product that reads beyond the stride, `range` on a product that is no JET, n_colours < 0; and, for n > 0 and
+ * n_products > 0: a NULL frame / out (palette with a PALETTE product and n_colours > 0), out_bytes below the layout's total, a frame or range not
+ * 4-byte aligned or an `out` not 16-byte aligned, `out` overlapping the frame, the palette or a range.  INERF_E_UNSUPPORTED:
+ * products that read a column beyond the 31st, n beyond 2^31 - 1 workgroups.  n == 0 or n_products == 0 is a no-op. */
+int inerf_frame_products(const inerf_frame_products_args* args, void* stream);
+
+/* minmax[0] = nanmin, minmax[1] = nanmax over values[i * stride], i < n, in fp32: NaNs are skipped, +-inf take part, a column
+ * that is all NaN gives (NaN, NaN) - a JET product then paints black.  accumulate != 0: the pair minmax holds on entry takes part
+ * (the range over a sequence of frames; start it from (NaN, NaN) or from a call with accumulate == 0).  Two launches: one pair per
+ * workgroup into `workspace` (inerf_frame_range_workspace_bytes(n) bytes, else INERF_E_WORKSPACE), then one workgroup over the
+ * pairs.  No floating-point atomic; a minimum has no order, so the result is the same on every run.  INERF_E_INVALID: n < 0,
+ * stride < 1, a NULL or misaligned values / minmax, buffers that overlap.  n == 0 is a no-op (minmax is left as it is). */
+int64_t inerf_frame_range_workspace_bytes(int64_t n);
+int inerf_frame_range(const float* values, int64_t stride, int64_t n, float* minmax, void* workspace, int64_t workspace_bytes,
+                      int accumulate, void* stream);
+
+/* The 768 bytes of JET[256][3] (host memory, static). */
+const unsigned char* inerf_jet_table(void);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40023          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40024          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -157,6 +157,25 @@ IMQ_SUMS, IMQ_COUNTS = 7, 3
 IMQ_SUM_NAMES = ("spp", "spg", "sgg", "sq_diff", "lmse_num", "lmse_den", "ssim_sum")
 IMQ_COUNT_NAMES = ("n_valid", "n_windows", "n_ssim")
 
+
+class FrameProduct(C.Structure):
+    """inerf_frame_product: one image plane made from columns of a packed frame (include/inerf.h, inerf_frame_products)."""
+    _fields_ = [("kind", C.c_int32), ("column", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32), ("a", C.c_float),
+                ("b", C.c_float), ("range", C.c_void_p), ("offset", C.c_int64)]
+
+
+FRAME_MAX_PRODUCTS = 16
+FRAME_TO8B, FRAME_U16, FRAME_U8_CAST, FRAME_THRESH, FRAME_PALETTE, FRAME_JET = range(6)
+FRAME_KIND_NAMES = ("to8b", "u16", "u8_cast", "thresh", "palette", "jet")
+FRAME_BYTES_PER_PIXEL = {FRAME_U16: 2, FRAME_U8_CAST: 1, FRAME_THRESH: 1, FRAME_PALETTE: 3, FRAME_JET: 3}      # TO8B: its width
+
+
+class FrameProductsArgs(C.Structure):
+    """inerf_frame_products_args: all image planes of one frame in one launch (include/inerf.h, inerf_frame_products)."""
+    _fields_ = [("frame", C.c_void_p), ("stride", C.c_int64), ("n", C.c_int64), ("n_products", C.c_int32), ("n_colours", C.c_int32),
+                ("palette", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_int64), ("products", FrameProduct * FRAME_MAX_PRODUCTS)]
+
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -267,6 +286,11 @@ SYMBOLS = {
     "inerf_eval_accumulate": (_I, [C.POINTER(EvalArgs), _P]),
     "inerf_image_quality_workspace_bytes": (_L, [_L, _L, _L, _I, _I, _I]),
     "inerf_image_quality": (_I, [C.POINTER(ImqArgs), _P]),
+    "inerf_frame_products_layout": (_L, [C.POINTER(FrameProductsArgs)]),
+    "inerf_frame_products": (_I, [C.POINTER(FrameProductsArgs), _P]),
+    "inerf_frame_range_workspace_bytes": (_L, [_L]),
+    "inerf_frame_range": (_I, [_P, _L, _L, _P, _P, _L, _I, _P]),
+    "inerf_jet_table": (C.POINTER(C.c_ubyte * 768), []),
 }
 
 _lib = None

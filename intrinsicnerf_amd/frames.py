@@ -5,7 +5,9 @@ image, then pull each map to the host with its own ``.cpu().numpy()`` - six bloc
 of which first waits for the whole render.  Here a frame's maps are packed into ONE device tensor, copied into one of two
 pinned host buffers on a side stream, and the next frame's kernels are enqueued while that copy runs; the host touches a
 frame only when the frame after it has been enqueued.  ``to8b`` happens on the device when only 8-bit images are wanted
-(``inerf_frame_to_u8``), a quarter of the bytes.  The ray batch of a pose comes from ``inerf_gen_rays`` (``inerf_gen_rays_ndc`` for NDC frames).
+(``inerf_frame_to_u8``), a quarter of the bytes; ``FrameProducts`` (opt-in) makes every 8- and 16-bit image of the loops - the
+16-bit casts, the label colours, the (acc > 10) mask and the jet maps of ``depth2rgb`` included - in one launch per frame
+(``inerf_frame_products``).  The ray batch of a pose comes from ``inerf_gen_rays`` (``inerf_gen_rays_ndc`` for NDC frames).
 """
 import os
 import struct
@@ -128,6 +130,141 @@ def to8b(x):
     if isinstance(x, torch.Tensor):
         return kernels.frame_to_u8(x.float().contiguous()) if x.is_cuda else (255 * torch.clamp(x, 0, 1)).to(torch.uint8)
     return (255 * np.clip(x, 0, 1)).astype(np.uint8)
+
+
+class FrameProducts:
+    """The 8- and 16-bit images of a render_path loop, made on the device from each frame's pack (csrc/frame_vis.hip): one
+    ``inerf_frame_products`` launch per frame, preceded by one ``inerf_frame_range`` per jet product that colours a map by its
+    own range; the bytes travel through a ``FrameStreamer`` of their own.  Opt-in; both front-ends read one
+    (``ssr.SSRRenderMixin.frame_products``, ``object_level.render_path(products=...)``) and hand it their product list.
+
+    A product is ``(name, kind, key[, parameter])`` over the pack's ``keys``:
+      ``(name, "to8b", key)``            uint8, [H, W] or [H, W, 3] with the map's width: ``to8b``
+      ``(name, "u16", key, scale)``      uint16 [H, W]: ``(map * scale).astype(np.uint16)``
+      ``(name, "u8_cast", key)``         uint8 [H, W]: ``map.astype(np.uint8)``
+      ``(name, "thresh", key, t)``       uint8 [H, W]: ``to8b(float32(map > t))``
+      ``(name, "palette", key)``         uint8 [H, W, 3]: ``palette[map]``, black outside the palette
+      ``(name, "jet", key, (lo, hi))``   uint8 [H, W, 3]: ``depth2rgb(map, lo, hi)``; ``None`` instead of the pair: the map's own range
+    """
+
+    KINDS = {name: k for k, name in enumerate(kernels._capi.FRAME_KIND_NAMES)}
+
+    def __init__(self):
+        self.names = None
+
+    def begin(self, products, keys, widths, image_shape, device, palette=None):
+        """Starts a pass: ``products`` over a pack of ``keys`` / ``widths`` (``pack_maps``) whose rows are the pixels of an
+        ``image_shape`` = (H, W) frame.  ``palette``: uint8 [C, 3] (numpy or tensor), copied to the device once."""
+        capi = kernels._capi
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"FrameProducts on {device}: intrinsicnerf_amd runs only on a HIP device (no CPU / eager fallback exists)")
+        start, c = {}, 0
+        for k, w in zip(keys, widths):
+            start[k] = (c, int(w))
+            c += int(w)
+        self.device, self.shape, self.columns = device, (int(image_shape[0]), int(image_shape[1])), c
+        self.n = self.shape[0] * self.shape[1]
+        self.palette = None
+        if palette is not None:
+            palette = palette.detach() if isinstance(palette, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(palette))
+            self.palette = palette.to(device=device, dtype=torch.uint8).reshape(-1, 3).contiguous()
+        self.names, self.kinds, self.ranged, specs = [], [], [], []
+        for spec in products:
+            name, kind, key = spec[0], self.KINDS[spec[1]], spec[2]
+            if key not in start:
+                raise KeyError(f"product {name!r} reads {key!r}; the pack holds {list(keys)}")
+            if name in self.names:
+                raise ValueError(f"two products are called {name!r}")
+            column, width = start[key]
+            a = b = 0.0
+            rng = None
+            if kind in (capi.FRAME_U16, capi.FRAME_THRESH):
+                a = float(spec[3])
+            elif kind == capi.FRAME_JET:
+                if len(spec) > 3 and spec[3] is not None:
+                    a, b = float(spec[3][0]), float(spec[3][1])
+                else:
+                    rng = torch.full((2,), float("nan"), dtype=torch.float32, device=device)
+                    self.ranged.append((column, rng))
+            elif kind == capi.FRAME_PALETTE and self.palette is None:
+                raise ValueError(f"product {name!r} is a palette gather: begin() needs the palette")
+            self.names.append(name)
+            self.kinds.append((kind, width))
+            specs.append((kind, column, width, a, b, rng))
+        self.plan = kernels.frame_products_plan(self.n, specs, 0 if self.palette is None else self.palette.shape[0])
+        self.workspace = torch.empty(max(kernels.frame_range_workspace_bytes(self.n) // 4, 1), dtype=torch.float32, device=device)
+        self.streamer, self.in_flight, self.host = FrameStreamer(device), [], {}
+
+    def add_frame(self, i, pack):
+        """Frame ``i``'s pack ([H * W, columns] fp32 on the device) is complete on the current stream: its planes are computed
+        there and their copy to the host is enqueued.  Nothing waits."""
+        if self.names is None:
+            raise RuntimeError("FrameProducts.add_frame before begin")
+        if not pack.is_cuda:
+            raise RuntimeError(f"FrameProducts.add_frame: the pack lives on {pack.device}; the frame images are made only on a HIP "
+                               "device (no CPU / eager fallback exists)")
+        if tuple(pack.shape) != (self.n, self.columns):
+            raise ValueError(f"the pack has shape {tuple(pack.shape)}, begin() was told {(self.n, self.columns)}")
+        for column, rng in self.ranged:           # the map's own range, on the device: the product kernel reads it
+            kernels.frame_range(pack[:, column], minmax=rng, workspace=self.workspace)
+        out, _ = kernels.frame_products(pack, None, palette=self.palette, plan=self.plan)
+        done = self.streamer.push(out)
+        self.in_flight.append(int(i))
+        if done is not None:
+            self.host[self.in_flight.pop(0)] = done
+
+    def images(self, i):
+        """``{name: array}`` of frame ``i``: views of the frame's host bytes - uint8 [H, W] / [H, W, 3], uint16 [H, W].  Waits for
+        the copies up to frame ``i`` alone; a frame is handed out once."""
+        i = int(i)
+        while i not in self.host:
+            if not self.in_flight:
+                raise KeyError(f"FrameProducts.images({i}): no such frame in flight")
+            self.host[self.in_flight.pop(0)] = self.streamer.pop()
+        buf = self.host.pop(i)
+        capi, out = kernels._capi, {}
+        for name, (kind, width), (offset, size) in zip(self.names, self.kinds, self.plan[1]):
+            plane = buf[offset:offset + size]
+            if kind == capi.FRAME_U16:
+                out[name] = plane.view("<u2").reshape(self.shape)
+            elif kind in (capi.FRAME_PALETTE, capi.FRAME_JET) or width == 3:
+                out[name] = plane.reshape(*self.shape, 3)
+            else:
+                out[name] = plane.reshape(self.shape)
+        return out
+
+
+def depth2rgb(depth, min_value=None, max_value=None):
+    """``imgviz.depth2rgb(depth, min_value=None, max_value=None)`` without imgviz or matplotlib: the jet colour map of
+    ``(depth - lo) / (hi - lo)``, black where that is NaN; ``lo`` / ``hi`` default to the map's nanmin / nanmax.  fp32 throughout,
+    the rule of include/inerf.h (JET).  A device tensor goes through ``inerf_frame_range`` / ``inerf_frame_products`` and comes
+    back as a uint8 device tensor ``[..., 3]``; a host array through the same rule in numpy with the library's table."""
+    if isinstance(depth, torch.Tensor) and depth.is_cuda:
+        flat = depth.detach().float().reshape(-1, 1)
+        if min_value is None or max_value is None:
+            rng = kernels.frame_range(flat[:, 0])
+            if min_value is not None:
+                rng[0] = float(min_value)
+            if max_value is not None:
+                rng[1] = float(max_value)
+            spec = (kernels._capi.FRAME_JET, 0, 1, 0.0, 0.0, rng)
+        else:
+            spec = (kernels._capi.FRAME_JET, 0, 1, float(min_value), float(max_value), None)
+        out, planes = kernels.frame_products(flat, [spec])
+        return out[planes[0][0]:planes[0][0] + planes[0][1]].reshape(*depth.shape, 3)
+    x = np.asarray(depth.detach().numpy() if isinstance(depth, torch.Tensor) else depth, dtype=np.float32)
+    import warnings
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)          # (an all-NaN map: its range is NaN and the image black)
+        lo = np.float32(np.nanmin(x) if min_value is None else min_value) if x.size else np.float32("nan")
+        hi = np.float32(np.nanmax(x) if max_value is None else max_value) if x.size else np.float32("nan")
+        t = (x - lo) / (hi - lo)
+        nan = np.isnan(t)
+        c = np.minimum(np.maximum(np.where(nan, np.float32(0), t), np.float32(0)), np.float32(1))
+        rgb = kernels.jet_table()[np.minimum((c * np.float32(256)).astype(np.int32), 255)]
+    rgb[nan] = 0
+    return rgb
 
 
 def ensure_dir(path):

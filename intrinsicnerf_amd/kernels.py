@@ -2000,3 +2000,126 @@ def image_quality(pred, target, mask=None, shape=None, window_size=20, window_sh
         rc = _capi.lib().inerf_image_quality(C.byref(a), _stream(sums))
     _capi.check(rc, "inerf_image_quality")
     return sums, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# frame images (csrc/frame_vis.hip): the 8- and 16-bit planes of one packed frame in one launch.  A product is
+# ``(kind, column, width, a, b, range)``: kind one of _capi.FRAME_*, ``range`` None or a device float32[2] tensor (JET: the
+# (lo, hi) the kernel reads instead of (a, b) - ``frame_range`` writes one)
+# ---------------------------------------------------------------------------------------------------------------------
+def frame_products_plan(n, products, n_colours=0):
+    """Host only (``inerf_frame_products_layout``; no device is touched): ``(args, planes, total)`` - an inerf_frame_products_args
+    with ``n``, the products and their offsets filled in, ``planes`` = [(offset, bytes)] per product (every offset a multiple of 16)
+    and the byte count the output needs."""
+    products = list(products)
+    if len(products) > _capi.FRAME_MAX_PRODUCTS:
+        raise ValueError(f"{len(products)} products: one launch takes at most {_capi.FRAME_MAX_PRODUCTS}")
+    a = _capi.FrameProductsArgs()
+    a.n, a.n_products, a.n_colours = int(n), len(products), int(n_colours)
+    held = []
+    for k, (kind, column, width, pa, pb, rng) in enumerate(products):
+        p = a.products[k]
+        p.kind, p.column, p.width, p.a, p.b = int(kind), int(column), int(width), float(pa), float(pb)
+        if rng is not None:
+            if not (isinstance(rng, torch.Tensor) and rng.dtype == torch.float32 and rng.numel() == 2 and rng.is_contiguous()):
+                raise ValueError(f"product {k}: range must be a contiguous float32 tensor of 2 values (lo, hi)")
+            p.range = rng.data_ptr()
+            held.append(rng)
+    total = int(_capi.lib().inerf_frame_products_layout(C.byref(a)))
+    if total < 0:
+        _capi.check(total, "inerf_frame_products_layout")
+    a.held = held                                          # the range tensors stay referenced as long as the args do
+    planes = []
+    for k in range(len(products)):
+        p = a.products[k]
+        bpp = p.width if p.kind == _capi.FRAME_TO8B else _capi.FRAME_BYTES_PER_PIXEL[p.kind]
+        planes.append((int(p.offset), int(n) * bpp))
+    return a, planes, total
+
+
+def frame_products(frame, products, palette=None, out=None, plan=None):
+    """All image planes of one packed frame in one launch of ``inerf_frame_products``.  ``frame``: [n, stride] fp32 on the device -
+    a view is taken as it is (unit stride along a row, any row stride); ``palette``: uint8 [C, 3] on the device, for PALETTE
+    products; ``out``: a contiguous uint8 tensor of at least the plan's total (allocated when not given); ``plan``: what
+    ``frame_products_plan(n, products, C)`` returned, to skip planning per frame.  Returns ``(out, planes)``, ``planes`` =
+    [(offset, bytes)] per product."""
+    if not (isinstance(frame, torch.Tensor) and frame.dim() == 2):
+        raise ValueError("frame must be a [n, stride] tensor" if isinstance(frame, torch.Tensor) else "frame must be a torch.Tensor")
+    if frame.dtype != torch.float32:
+        raise ValueError(f"frame must be float32, got {frame.dtype}")
+    n = int(frame.shape[0])
+    if n > 0 and frame.shape[1] > 0 and frame.stride(1) != 1:
+        raise ValueError(f"frame must have unit stride along its rows, got stride {frame.stride(1)}")
+    if n > 1 and frame.stride(0) < frame.shape[1]:
+        raise ValueError(f"frame has a row stride of {frame.stride(0)} floats, smaller than its width {frame.shape[1]}")
+    stride = int(frame.stride(0)) if n > 1 else max(int(frame.shape[1]), 1)
+    named = [("frame", frame)]
+    n_colours = 0
+    if palette is not None:
+        if not (isinstance(palette, torch.Tensor) and palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3
+                and palette.is_contiguous()):
+            raise ValueError("palette must be a contiguous uint8 [C, 3] tensor")
+        n_colours = int(palette.shape[0])
+        named.append(("palette", palette))
+    a, planes, total = plan if plan is not None else frame_products_plan(n, products, n_colours)
+    if a.n != n or a.n_colours != n_colours:
+        raise ValueError(f"the plan was made for {a.n} pixels and {a.n_colours} colours, the frame holds {n} and the palette {n_colours}")
+    for k in range(a.n_products):
+        p = a.products[k]
+        if p.column < 0 or p.column + p.width > frame.shape[1]:
+            raise ValueError(f"product {k} reads columns {p.column} .. {p.column + p.width - 1} of a frame with {frame.shape[1]}")
+        if p.kind == _capi.FRAME_PALETTE and palette is None:
+            raise ValueError(f"product {k} is a palette gather: pass palette")
+    named += [(f"range of product {k}", t) for k, t in enumerate(a.held)]
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=frame.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= total):
+        raise ValueError(f"out must be a contiguous uint8 tensor of at least {total} bytes")
+    named.append(("out", out))
+    device = _eval_devices(named)
+    a.frame, a.stride = frame.data_ptr(), stride
+    a.palette = palette.data_ptr() if palette is not None else None
+    a.out, a.out_bytes = out.data_ptr(), out.numel()
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_frame_products(C.byref(a), _stream(frame))
+    _capi.check(rc, "inerf_frame_products")
+    return out, planes
+
+
+def frame_range_workspace_bytes(n):
+    return int(_capi.lib().inerf_frame_range_workspace_bytes(int(n)))
+
+
+def frame_range(values, minmax=None, accumulate=False, workspace=None):
+    """``(nanmin, nanmax)`` of ``values`` ([n] fp32 on the device, any element stride: a column of a pack) into ``minmax`` (float32
+    [2] on the device, allocated when not given) - two launches of ``inerf_frame_range``, no host synchronisation.  ``accumulate``:
+    the pair ``minmax`` holds takes part (the range over several frames).  ``workspace``: a contiguous float32 tensor of at least
+    ``frame_range_workspace_bytes(n)`` bytes (allocated when not given).  Returns ``minmax``."""
+    values, stride = _eval_view(values, "values", 1)
+    n = int(values.shape[0])
+    named = [("values", values)]
+    if minmax is None:
+        if accumulate:
+            raise ValueError("accumulate needs the minmax to accumulate into")
+        minmax = torch.full((2,), float("nan"), dtype=torch.float32, device=values.device)
+    elif not (isinstance(minmax, torch.Tensor) and minmax.dtype == torch.float32 and minmax.numel() == 2 and minmax.is_contiguous()):
+        raise ValueError("minmax must be a contiguous float32 tensor of 2 values")
+    named.append(("minmax", minmax))
+    need = frame_range_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 1), dtype=torch.float32, device=values.device)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.float32 and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous float32 tensor")
+    named.append(("workspace", workspace))
+    device = _eval_devices(named)
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_frame_range(_ptr(values), stride, n, _ptr(minmax), _ptr(workspace), workspace.numel() * 4,
+                                           int(bool(accumulate)), _stream(values))
+    _capi.check(rc, "inerf_frame_range")
+    return minmax
+
+
+def jet_table():
+    """JET[256, 3] uint8 (numpy) - the colour table of the JET products, from the library (csrc/jet_table.h)."""
+    import numpy as np
+    return np.frombuffer(bytes(_capi.lib().inerf_jet_table().contents), dtype=np.uint8).reshape(256, 3).copy()

@@ -62,6 +62,11 @@ reference's validation step run on a current numpy: its own function uses ``np.f
 ``evaluation.FrameEvaluator`` into the unedited trainer is out of scope - which ray set pairs with which targets is the trainer's
 knowledge (INTEGRATION.md has the four lines).  ``run_nerf.py`` has no metric functions: the flag only says so, once.
 
+``--inerf-frame-products`` (opt-in; takes effect only together with ``--inerf-render-path``) makes every 8- and 16-bit image of the
+mirrors' ``render_path`` on the device (``frames.FrameProducts``, csrc/frame_vis.hip): the mirrors get ``products=`` (object level)
+and ``SSRTrainer.frame_products`` (SSR).  The SSR trainer's ``vis_deps`` / ``vis_entropys`` and its ``vis_depth_*`` / ``vis_entropy_*``
+files then need no imgviz at run time.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -177,7 +182,8 @@ class _TrainerDraws:
         return state
 
 
-def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False, cluster_refresh=False):
+def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False, cluster_refresh=False,
+                        frame_products=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
     cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
@@ -203,7 +209,14 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
         if cluster_refresh:
             from . import refresh
             extra["refresh"] = refresh.ClusterRefresh(manager_factory=factory)
+        if frame_products:
+            from . import frames
+            extra["products"] = frames.FrameProducts()
         namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=factory, **extra)
+    elif with_render_path and frame_products:
+        import functools
+        from . import frames
+        namespace["render_path"] = functools.partial(object_level.render_path, products=frames.FrameProducts())
     return names
 
 
@@ -225,7 +238,8 @@ def rebind_eval():
     return bound
 
 
-def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False, evaluate=False):
+def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False, evaluate=False,
+               frame_products=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
@@ -244,6 +258,10 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
             from . import refresh
             trainer.SSRTrainer.cluster_refresh = refresh.ClusterRefresh(manager_factory=factory)
     bound["SSR.training.trainer.SSRTrainer"] = list(methods)
+    if with_render_path and frame_products:            # read by the mirror's render_path (ssr.SSRRenderMixin.frame_products is None)
+        from . import frames
+        trainer.SSRTrainer.frame_products = frames.FrameProducts()
+        bound["SSR.training.trainer.SSRTrainer"].append("frame_products")
     for mod_name in SSR_MODULES:
         mod = sys.modules.get(mod_name)
         if mod is None:
@@ -303,7 +321,7 @@ def _object_eval_notice():
 
 
 def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False,
-            evaluate=False):
+            evaluate=False, frame_products=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -316,8 +334,10 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     mod.__file__ = script
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
+    products = dict(frame_products=True) if frame_products else {}      # (only when given, as `evaluate` below)
     if kind == "object":
-        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws, cluster_refresh)
+        mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws, cluster_refresh,
+                                                              **products)
         if batches:
             _object_batches_notice()
         if evaluate:
@@ -325,6 +345,7 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     else:
         importlib.import_module("SSR.training.trainer")
         extra = dict(evaluate=True) if evaluate else {}           # (only when given: a stand-in rebind_ssr of the older signature keeps working)
+        extra.update(products)
         mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws, cluster_refresh, **extra)
     return mod, main
 
@@ -355,6 +376,9 @@ def main(argv=None):
     evaluate = "--inerf-eval" in argv
     if evaluate:
         argv.remove("--inerf-eval")
+    frame_products = "--inerf-frame-products" in argv
+    if frame_products:
+        argv.remove("--inerf-frame-products")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -371,6 +395,8 @@ def main(argv=None):
         extra["cluster_refresh"] = True
     if evaluate:
         extra["evaluate"] = True
+    if frame_products:
+        extra["frame_products"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

@@ -416,7 +416,7 @@ def to8b(x):
 
 
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0, update_cluster=False,
-                b_f=0.5, cluster_manager_factory=None, refresh=None, evaluator=None):
+                b_f=0.5, cluster_manager_factory=None, refresh=None, evaluator=None, products=None):
     """Render every pose of ``render_poses`` - run_nerf.py:142-272; returns ``(rgbs, disps, cluster_manager)``.
 
     Same arguments, same returned stacks (``[N, H, W, 3]`` / ``[N, H, W]`` float32 numpy), same files in ``savedir``
@@ -430,7 +430,12 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     returned values, same files; no ``cluster_manager_factory`` is needed then.  ``evaluator`` (an
     ``evaluation.FrameEvaluator``; opt-in): when it holds targets registered for ``render_poses``, every frame's rgb, albedo and
     shading columns are handed to its ``add_frame`` from the device pack, before the host copy - the reference has no metric code
-    here (its PSNR line is commented out, run_nerf.py:187-191) and ``gt_imgs`` stays unread; read ``evaluator.results()`` afterwards."""
+    here (its PSNR line is commented out, run_nerf.py:187-191) and ``gt_imgs`` stays unread; read ``evaluator.results()`` afterwards.
+    ``products`` (a ``frames.FrameProducts``; opt-in): the five 8-bit images of a frame - ``{:03d}``, ``a``, ``s``, ``res`` and the
+    ``(acc > 10)`` mask ``acc`` - are made on the device in one launch (csrc/frame_vis.hip) and travel as 11 bytes per pixel.  When no
+    host-side cluster fit reads the other maps - ``update_cluster`` off, or ``refresh`` given with every pack inside its
+    ``keep_bytes`` (``ClusterRefresh.keeps_all``, asked with the first pack's size) - only the columns of the returned
+    ``(rgbs, disps)`` travel as floats: 4 floats + 11 bytes per pixel instead of the pack's 12 floats."""
     import os
     from . import frames
     H, W, focal = hwf
@@ -445,6 +450,14 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     widths = None
 
     def finish(i, frame):
+        if imaging:         # the five 8-bit images come from the device planes
+            planes = products.images(i)
+            for prefix in ("", "a", "s", "res", "acc"):
+                frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), planes[prefix])
+        if slim:            # the frame holds the rgb and disp columns alone
+            m = frames.unpack_frame(frame, widths[:2], keys[:2], (H, W))
+            rgbs.append(m["rgb_map"]); disps.append(m["disp_map"])
+            return
         m = frames.unpack_frame(frame, widths, keys, (H, W))
         rgbs.append(m["rgb_map"]); disps.append(m["disp_map"]); albedos.append(m["albedo_map"])
         shadings.append(m["shading_map"]); residuals.append(m["residual_map"])
@@ -454,11 +467,15 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         if update_cluster and not on_device:
             sample_pixels.append(albedos[-1][::2, ::2, :].reshape(-1, 3))
             sample_labels.append(label[::2, ::2].reshape(-1, 1))
-        if savedir is not None:
+        if savedir is not None and not imaging:
             for prefix, img in (("", rgbs[-1]), ("a", albedos[-1]), ("s", shadings[-1]), ("res", residuals[-1]), ("acc", accs[-1])):
                 frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), frames.to8b(img))
 
     on_device = bool(update_cluster) and refresh is not None
+    # with products, the float maps beyond rgb and disp are read on the host only by a host-side cluster fit, or by the refresh
+    # pass for a frame whose pack it could not keep on the device (decided at the first frame, from the pack's real size)
+    slim = products is not None and not update_cluster
+    imaging = products is not None and savedir is not None            # (without savedir nobody looks at the images)
     evaluating = evaluator is not None and evaluator.begin(render_poses)
     streamer, in_flight = None, []
     for i, c2w in enumerate(render_poses):
@@ -470,15 +487,27 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
                                    "HIP device (no CPU / eager fallback exists)")
             if i == 0:                                   # class_num == 1 (run_nerf.py:218): the (acc > 10) label is not read
                 refresh.begin(len(render_poses), H, W, 1, pack.device)
+                # the refresh pass reads host maps only for a frame whose pack it did not keep: its own rule says whether one will be
+                keeps_all = getattr(refresh, "keeps_all", None)
+                slim = products is not None and keeps_all is not None and keeps_all(len(render_poses), pack.numel() * pack.element_size())
             refresh.add_frame(i, pack, widths, keys)
         if evaluating:
             start = {k: sum(widths[:j]) for j, k in enumerate(keys)}
             cols = {k: pack[:, start[k]:start[k] + widths[j]] for j, k in enumerate(keys)}
             evaluator.add_frame(i, rgb=cols["rgb_map"], albedo=cols["albedo_map"], shading=cols["shading_map"])
+        if products is not None and not pack.is_cuda:
+            raise RuntimeError(f"render_path(products=...): the rendered maps live on {pack.device}; the frame images are made only on a "
+                               "HIP device (no CPU / eager fallback exists)")
+        if imaging:
+            if i == 0:
+                products.begin([("", "to8b", "rgb_map"), ("a", "to8b", "albedo_map"), ("s", "to8b", "shading_map"),
+                                ("res", "to8b", "residual_map"), ("acc", "thresh", "acc_map", 10.0)],           # run_nerf.py:173
+                               keys, widths, (H, W), pack.device)
+            products.add_frame(i, pack)
         if pack.is_cuda:
             if streamer is None:
                 streamer = frames.FrameStreamer(pack.device)
-            done = streamer.push(pack)
+            done = streamer.push(pack[:, :4].contiguous() if slim else pack)          # slim: rgb_map and disp_map lead the pack
             in_flight.append(i)
             if done is not None:
                 finish(in_flight.pop(0), done)
@@ -490,9 +519,9 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     cluster_manager = None
     if on_device:
         # the sample table was filled frame by frame; the fit reads it where it is, and every kept pack becomes its two 8-bit images
-        cluster_manager = refresh.finish(b_f, host=lambda i: (albedos[i], None, shadings[i], residuals[i]))
+        cluster_manager = refresh.finish(b_f, host=None if slim else (lambda i: (albedos[i], None, shadings[i], residuals[i])))
         if savedir is not None:
-            for i in range(len(albedos)):
+            for i in range(len(rgbs)):
                 c, edit = refresh.snap(i)
                 frames.write_png(os.path.join(savedir, "c{:03d}.png".format(i)), c)
                 frames.write_png(os.path.join(savedir, "edit{:03d}.png".format(i)), edit)

@@ -90,6 +90,11 @@ class ClusterRefresh:
             self._kept[i], self._cols[i] = pack, cols
             self._held += size
 
+    def keeps_all(self, n_frames, pack_bytes):
+        """True when ``add_frame`` will keep the pack of every one of ``n_frames`` frames of ``pack_bytes`` bytes each for ``snap`` -
+        its own budget rule, counted from ``begin``: ``finish`` then needs no ``host`` arrays."""
+        return self._held + int(n_frames) * int(pack_bytes) <= self.keep_bytes
+
     def finish(self, b_f, host=None):
         """Builds the manager (``manager_factory(class_num=n_classes)``), fits it on the table and returns it.  ``host(i)`` ->
         ``(albedo [H, W, 3], label [H, W] or None, shading [H, W], residual [H, W, 3])`` numpy arrays of frame ``i``: read by

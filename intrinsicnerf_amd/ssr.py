@@ -229,6 +229,7 @@ class SSRRenderMixin:
     return_raw = True
     check_numerics = True
     cluster_refresh = None        # a refresh.ClusterRefresh: render_path(update_cluster=True) keeps its sample set, fit and c / edit images on the device
+    frame_products = None         # a frames.FrameProducts: render_path takes every 8- / 16-bit image - the jet maps of depth and entropy included, no imgviz - from csrc/frame_vis.hip
     frame_evaluator = None        # an evaluation.FrameEvaluator: render_path takes the label / entropy maps from csrc/eval.hip and accumulates the metrics of registered frame sets
     # a draws.DrawState: in training mode the jitter, the per-ray u (perturb > 0) and the density noise (raw_noise_std > 0) are drawn inside
     # the kernels as a function of (seed, step, stream, global ray index, sample) - the same bits for any `chunk`; None: torch's generator
@@ -261,7 +262,12 @@ class SSRRenderMixin:
         ``refresh.ClusterRefresh``; opt-in): the sample set, the fit and the ``c*`` / ``edit*`` images then stay on the device
         (csrc/refresh.hip), with the same returned values and files.  ``self.frame_evaluator`` (an ``evaluation.FrameEvaluator``;
         opt-in): the two semantic maps come from one launch of csrc/eval.hip instead of the six torch expressions, and the metrics of
-        a frame set registered with it are accumulated in that launch; the returned tuple and the files keep shapes and dtypes."""
+        a frame set registered with it are accumulated in that launch; the returned tuple and the files keep shapes and dtypes.
+        ``self.frame_products`` (a ``frames.FrameProducts``; opt-in): the 8-bit rgb / albedo / shading / residual / entropy images, the
+        16-bit disp / depth images, ``label``, ``vis_label``, ``vis_depth`` and ``vis_entropy`` are made on the device in one launch per
+        frame (csrc/frame_vis.hip) and travel as bytes next to the float maps; the files are written from them and ``sems``,
+        ``vis_deps``, ``vis_sems``, ``vis_entropys`` returned from them - ``vis_deps`` / ``vis_entropys`` then need no imgviz
+        (``frames.depth2rgb``'s rule: jet over [near, far], and over the entropy map's own range)."""
         import os
         import numpy as np
         from . import frames
@@ -285,11 +291,19 @@ class SSRRenderMixin:
 
         def finish(i, frame):
             m = frames.unpack_frame(frame, widths, keys, (H, W))
+            img = products.images(i) if products is not None else None          # the frame's device-made planes
             acc["rgb"].append(m[f"rgb_{lvl}"]); acc["disp"].append(m[f"disp_{lvl}"]); acc["albedo"].append(m[f"albedo_{lvl}"])
             acc["shading"].append(m[f"shading_{lvl}"]); acc["residual"].append(m[f"residual_{lvl}"]); acc["dep"].append(m[f"depth_{lvl}"])
-            if depth2rgb is not None:
+            if img is not None:
+                acc["vis_dep"].append(img["vis_depth"])
+            elif depth2rgb is not None:
                 acc["vis_dep"].append(depth2rgb(acc["dep"][-1], min_value=self.near, max_value=self.far))
-            if self.enable_semantic:
+            if self.enable_semantic and img is not None:
+                acc["sem"].append(img["label"]); acc["ent"].append(m["sem_entropy"])
+                if cmap is not None:
+                    acc["vis_sem"].append(img["vis_label"])
+                acc["vis_ent"].append(img["vis_entropy"])
+            elif self.enable_semantic:
                 label = m["sem_label"].astype(np.uint8)
                 acc["sem"].append(label); acc["ent"].append(m["sem_entropy"])
                 if cmap is not None:
@@ -301,13 +315,17 @@ class SSRRenderMixin:
                 sample_labels.append(acc["sem"][-1][::2, ::2].reshape(-1, 1))
             if save_dir is not None:
                 w = lambda name, img: frames.write_png(os.path.join(save_dir, name.format(i)), img)
-                w("rgb_{:03d}.png", frames.to8b(acc["rgb"][-1])); w("albedo_{:03d}.png", frames.to8b(acc["albedo"][-1]))
-                w("shading_{:03d}.png", frames.to8b(acc["shading"][-1])); w("residual_{:03d}.png", frames.to8b(acc["residual"][-1]))
-                w("disp_{:03d}.png", acc["disp"][-1].astype(np.uint16)); w("depth_{:03d}.png", (acc["dep"][-1] * 1000).astype(np.uint16))
+                if img is not None:
+                    for name in ("rgb", "albedo", "shading", "residual", "disp", "depth"):
+                        w(name + "_{:03d}.png", img[name])
+                else:
+                    w("rgb_{:03d}.png", frames.to8b(acc["rgb"][-1])); w("albedo_{:03d}.png", frames.to8b(acc["albedo"][-1]))
+                    w("shading_{:03d}.png", frames.to8b(acc["shading"][-1])); w("residual_{:03d}.png", frames.to8b(acc["residual"][-1]))
+                    w("disp_{:03d}.png", acc["disp"][-1].astype(np.uint16)); w("depth_{:03d}.png", (acc["dep"][-1] * 1000).astype(np.uint16))
                 if acc["vis_dep"]:
                     w("vis_depth_{:03d}.png", acc["vis_dep"][-1])
                 if self.enable_semantic:
-                    w("label_{:03d}.png", acc["sem"][-1]); w("entropy_{:03d}.png", frames.to8b(acc["ent"][-1]))
+                    w("label_{:03d}.png", acc["sem"][-1]); w("entropy_{:03d}.png", img["entropy"] if img is not None else frames.to8b(acc["ent"][-1]))
                     if acc["vis_sem"]:
                         w("vis_label_{:03d}.png", acc["vis_sem"][-1])
                     if acc["vis_ent"]:
@@ -320,6 +338,7 @@ class SSRRenderMixin:
         evaluator = getattr(self, "frame_evaluator", None)
         if evaluator is not None:
             evaluator.begin(rays)
+        products = getattr(self, "frame_products", None)
         for i in range(len(rays)):
             out = self.render_rays(rays[i])
             maps = {k: out[k].detach() for k in keys if k in out}
@@ -342,6 +361,21 @@ class SSRRenderMixin:
                 if i == 0:
                     refresh.begin(len(rays), H, W, class_num, pack.device)
                 refresh.add_frame(i, pack, widths, keys)
+            if products is not None:
+                if not pack.is_cuda:
+                    raise RuntimeError(f"render_path with frame_products: the rendered maps live on {pack.device}; the frame images are "
+                                       "made only on a HIP device (no CPU / eager fallback exists)")
+                if i == 0:
+                    plist = [(k, "to8b", f"{k}_{lvl}") for k in ("rgb", "albedo", "shading", "residual")]
+                    plist += [("disp", "u16", f"disp_{lvl}", 1.0), ("depth", "u16", f"depth_{lvl}", 1000.0),      # trainer.py:1344-1345
+                              ("vis_depth", "jet", f"depth_{lvl}", (float(self.near), float(self.far)))]            # trainer.py:1314
+                    if self.enable_semantic:
+                        plist += [("label", "u8_cast", "sem_label"), ("entropy", "to8b", "sem_entropy"),
+                                  ("vis_entropy", "jet", "sem_entropy", None)]                                       # trainer.py:1321: its own range
+                        if cmap is not None:
+                            plist.append(("vis_label", "palette", "sem_label"))                                     # trainer.py:1269, 1294
+                    products.begin(plist, keys, widths, (H, W), pack.device, palette=cmap)
+                products.add_frame(i, pack)
             if pack.is_cuda:
                 if streamer is None:
                     streamer = frames.FrameStreamer(pack.device)
