@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40024
+#define INERF_ABI_VERSION 40025
 
 /* error codes */
 #define INERF_OK              0
@@ -1397,6 +1397,83 @@ int inerf_frame_range(const float* values, int64_t stride, int64_t n, float* min
 
 /* The 768 bytes of JET[256][3] (host memory, static). */
 const unsigned char* inerf_jet_table(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * PNG files on the device (csrc/png.hip, csrc/png_huff.h): up to 16 image planes - exactly what inerf_frame_products writes, so the
+ * encoder chains after that launch with no repacking - become 16 complete PNG files in `dst`, in three launches for all images
+ * together.  What render_path otherwise does on the host per file (zlib level 6 over rows of filter type 0).
+ * FILE      signature, IHDR, ONE IDAT, IEND, each with its CRC-32.  Colour type 0 (grey, 8 or 16 bit; 16-bit samples big-endian in
+ *           the file, little-endian in `src`) or 2 (RGB, 8 bit).  The IDAT is a zlib stream: 0x78 0x01, DEFLATE data, Adler-32.
+ * FILTER    per row; INERF_PNG_FILTER_ADAPTIVE takes the type 0 .. 4 with the smallest sum of min(b, 256 - b) over the row's
+ *           filtered bytes, ties to the lowest type.  Byte distance 1 (grey 8), 2 (grey 16), 3 (RGB); the row above row 0 is zero.
+ * SEGMENT   whole rows, as many as fit 32 768 filtered bytes (1 + width * channels * bit_depth / 8 per row); one workgroup each.
+ *           Segments are independent: no match reaches before a segment's first byte.
+ * TOKENS    literals and distance-1 matches.  A run of L >= 4 equal bytes is one literal and matches (3 .. 258) over the other
+ *           L - 1 bytes: 258s and the remainder; a remainder of 1 or 2 takes bytes from the last 258 and becomes a 3.
+ * CODE      one dynamic-Huffman block per segment: HLIT >= 257, HDIST = 1 (one distance code of 1 bit), HCLEN = 19, literal/length
+ *           lengths <= 15 and complete, code-length code <= 7 bits and complete, no repeat codes 16 / 17 / 18 in the header.  A
+ *           segment whose dynamic block is not smaller than a stored block (5 + bytes) is stored.  Every segment ends on a byte
+ *           boundary and is not final - an empty stored block follows a dynamic block that ends inside a byte; one final empty
+ *           stored block ends the stream.
+ * dst_capacity = 68 + height * (1 + width * channels * bit_depth / 8) + 5 * segments: the stored-everything bound - 8 signature,
+ * 25 IHDR, 12 IDAT frame, 2 zlib header, 5 final block, 4 Adler-32, 12 IEND; the filtered bytes; 5 per stored segment.
+ * sizes[k] <= dst_capacity always, and no byte of dst outside [dst_offset, dst_offset + dst_capacity) is written.
+ * Integer arithmetic only, LDS atomics are integer adds and ORs, no hand-off between workgroups (the stream orders the three
+ * launches): the bytes are the same on every run.  Nothing is allocated, synchronised or read on the host: capturable into a HIP
+ * graph.
+ * ------------------------------------------------------------------------------------------- */
+#define INERF_PNG_MAX_IMAGES 16
+#define INERF_PNG_FILTER_ADAPTIVE (-1)      /* else 0 .. 4: that PNG filter type on every row */
+
+typedef struct inerf_png_image {
+    int32_t height;
+    int32_t width;
+    int32_t channels;                /* 1 | 3 */
+    int32_t bit_depth;               /* 8 | 16; 16 only with channels == 1 */
+    int32_t filter;                  /* INERF_PNG_FILTER_ADAPTIVE or 0 .. 4 */
+    int32_t reserved;
+    int64_t src_offset;              /* of the plane in src, bytes (a product's `offset`); 16-bit planes little-endian */
+    int64_t dst_offset;              /* of the file in dst, bytes: written by inerf_png_layout (a multiple of 16) */
+    int64_t dst_capacity;            /* written by inerf_png_layout: the worst-case file length, see above */
+} inerf_png_image;
+
+typedef struct inerf_png_args {
+    const unsigned char* src;        /* the planes, device */
+    int64_t src_bytes;
+    unsigned char* dst;              /* the files, device, 16-byte aligned */
+    int64_t dst_bytes;
+    int64_t* sizes;                  /* device int64[n_images]: the length of file k, which starts at dst + images[k].dst_offset */
+    void* workspace;                 /* device, 16-byte aligned, inerf_png_workspace_bytes(args) bytes */
+    int64_t workspace_bytes;
+    int32_t n_images;                /* 0 .. INERF_PNG_MAX_IMAGES */
+    int32_t reserved;
+    inerf_png_image images[INERF_PNG_MAX_IMAGES];
+} inerf_png_args;
+
+/* Host only, no HIP call: writes images[k].dst_offset / dst_capacity and returns the byte count `dst` needs, or a negative error
+ * code: INERF_E_INVALID for NULL args, n_images outside 0 .. 16, height or width < 1, channels not 1 | 3, bit_depth not 8 | 16 or
+ * 16 with 3 channels, a filter outside -1 .. 4; INERF_E_UNSUPPORTED for a filtered row longer than a segment (32 768 bytes). */
+int64_t inerf_png_layout(inerf_png_args* args);
+
+/* Host only: the workspace the call needs (per segment a slot of 32 784 bytes and 32 bytes of bookkeeping), or the layout's error. */
+int64_t inerf_png_workspace_bytes(const inerf_png_args* args);
+
+/* Three launches: one workgroup per segment (filter, runs, code, bits; 74 KiB of LDS, two workgroups per CU), one workgroup that
+ * scans the segment lengths, combines the segments' Adler-32 sums and CRC-32 registers and writes headers, trailers and sizes, and
+ * one workgroup per segment that copies it to its place.  Checked before any HIP call.  INERF_E_INVALID: what inerf_png_layout
+ * refuses; dst_offset / dst_capacity that are not the layout's; src_bytes < 0 or a plane that runs past it; and, for n_images > 0:
+ * a NULL src / dst / sizes, dst_bytes below the layout's total, dst or workspace not 16-byte aligned, sizes not 8-byte aligned,
+ * dst, sizes or workspace overlapping src or each other.  INERF_E_WORKSPACE: a NULL or too small workspace.  n_images == 0 is a
+ * no-op. */
+int inerf_png_encode(const inerf_png_args* args, void* stream);
+
+/* Host only - the routine of csrc/png_huff.h that the segment kernel runs on one lane: code lengths of a minimum-redundancy prefix
+ * code over freq[0 .. n) with no length above `limit`.  A zero count gives length 0; one used symbol length 1; two or more a complete
+ * code (Kraft sum 1), the Huffman optimum whenever that fits the limit, else its lengths clamped and repaired (one code leaves the
+ * deepest level, one shorter code is split, until the Kraft sum is 1; the longest lengths go to the rarest symbols).  Ties are
+ * broken by the symbol index.  INERF_E_INVALID: NULL pointers, n outside 1 .. 288, limit outside 1 .. 15, more used symbols than
+ * 2^limit, counts whose sum exceeds 32 bits. */
+int inerf_png_code_lengths(const uint32_t* freq, int n, int limit, unsigned char* lengths);
 
 #ifdef __cplusplus
 }

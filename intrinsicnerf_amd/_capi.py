@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40024          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40025          # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -176,6 +176,24 @@ class FrameProductsArgs(C.Structure):
                 ("palette", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_int64), ("products", FrameProduct * FRAME_MAX_PRODUCTS)]
 
 
+class PngImage(C.Structure):
+    """inerf_png_image: one plane to encode and where its file goes (include/inerf.h, inerf_png_encode)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("bit_depth", C.c_int32), ("filter", C.c_int32),
+                ("reserved", C.c_int32), ("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("dst_capacity", C.c_int64)]
+
+
+PNG_MAX_IMAGES = 16
+PNG_FILTER_ADAPTIVE = -1
+PNG_SEGMENT_BYTES = 32768      # filtered bytes per segment (csrc/png.hip)
+
+
+class PngArgs(C.Structure):
+    """inerf_png_args: up to 16 planes -> 16 PNG files in three launches (include/inerf.h, inerf_png_encode)."""
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("dst", C.c_void_p), ("dst_bytes", C.c_int64), ("sizes", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_images", C.c_int32), ("reserved", C.c_int32),
+                ("images", PngImage * PNG_MAX_IMAGES)]
+
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -291,6 +309,10 @@ SYMBOLS = {
     "inerf_frame_range_workspace_bytes": (_L, [_L]),
     "inerf_frame_range": (_I, [_P, _L, _L, _P, _P, _L, _I, _P]),
     "inerf_jet_table": (C.POINTER(C.c_ubyte * 768), []),
+    "inerf_png_layout": (_L, [C.POINTER(PngArgs)]),
+    "inerf_png_workspace_bytes": (_L, [C.POINTER(PngArgs)]),
+    "inerf_png_encode": (_I, [C.POINTER(PngArgs), _P]),
+    "inerf_png_code_lengths": (_I, [C.POINTER(C.c_uint32), _I, _I, C.POINTER(C.c_ubyte)]),
 }
 
 _lib = None

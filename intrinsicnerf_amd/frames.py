@@ -7,7 +7,8 @@ pinned host buffers on a side stream, and the next frame's kernels are enqueued 
 frame only when the frame after it has been enqueued.  ``to8b`` happens on the device when only 8-bit images are wanted
 (``inerf_frame_to_u8``), a quarter of the bytes; ``FrameProducts`` (opt-in) makes every 8- and 16-bit image of the loops - the
 16-bit casts, the label colours, the (acc > 10) mask and the jet maps of ``depth2rgb`` included - in one launch per frame
-(``inerf_frame_products``).  The ray batch of a pose comes from ``inerf_gen_rays`` (``inerf_gen_rays_ndc`` for NDC frames).
+(``inerf_frame_products``), and with ``FrameProducts(encode=True)`` those planes become complete PNG files on the device too
+(``inerf_png_encode``, csrc/png.hip) - the host only writes bytes.  The ray batch of a pose comes from ``inerf_gen_rays`` (``inerf_gen_rays_ndc`` for NDC frames).
 """
 import os
 import struct
@@ -124,6 +125,27 @@ def write_png(path, image):
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def encode_png(image, filter=None):
+    """The PNG file (``bytes``) of a device tensor - uint8 [H, W] or [H, W, 3], uint16 [H, W] - encoded on the device
+    (``inerf_png_encode``).  ``filter``: a PNG filter type 0 .. 4 for every row; default: the adaptive choice per row.  Waits for the
+    file's length, then copies that many bytes."""
+    if not isinstance(image, torch.Tensor):
+        raise TypeError("encode_png takes a device tensor; write_png writes a numpy array")
+    if not image.is_cuda:
+        raise RuntimeError(f"encode_png: the image lives on {image.device}; PNG files are encoded only on a HIP device (no CPU / eager "
+                           "fallback exists)")
+    if image.dtype == torch.uint8 and (image.dim() == 2 or (image.dim() == 3 and image.shape[2] == 3)):
+        channels, depth = (1 if image.dim() == 2 else 3), 8
+    elif image.dtype == getattr(torch, "uint16", None) and image.dim() == 2:
+        channels, depth = 1, 16
+    else:
+        raise ValueError(f"encode_png: dtype {image.dtype}, shape {tuple(image.shape)}")
+    spec = (image.shape[0], image.shape[1], channels, depth, 0) + (() if filter is None else (int(filter),))
+    plan = kernels.png_plan([spec])
+    out, sizes = kernels.png_encode(image.contiguous().view(torch.uint8).reshape(-1), plan)
+    return out[:int(sizes[0])].cpu().numpy().tobytes()
+
+
 def to8b(x):
     """(255 * clip(x, 0, 1)).astype(uint8) - run_nerf_helpers.py:13: numpy arrays on the host, device tensors through
     ``inerf_frame_to_u8``."""
@@ -145,12 +167,17 @@ class FrameProducts:
       ``(name, "thresh", key, t)``       uint8 [H, W]: ``to8b(float32(map > t))``
       ``(name, "palette", key)``         uint8 [H, W, 3]: ``palette[map]``, black outside the palette
       ``(name, "jet", key, (lo, hi))``   uint8 [H, W, 3]: ``depth2rgb(map, lo, hi)``; ``None`` instead of the pair: the map's own range
+
+    ``encode=True``: every plane is also encoded to a PNG file on the device (``inerf_png_encode``: three more launches per frame,
+    adaptive row filter, one dynamic-Huffman block per 32 KiB segment); the files travel through a second ``FrameStreamer`` in their
+    worst-case buffers, with their lengths behind them, and ``files(i)`` hands out ``{name: bytes}``.  ``images(i)`` is unchanged.
     """
 
     KINDS = {name: k for k, name in enumerate(kernels._capi.FRAME_KIND_NAMES)}
 
-    def __init__(self):
+    def __init__(self, encode=False):
         self.names = None
+        self.encode = bool(encode)
 
     def begin(self, products, keys, widths, image_shape, device, palette=None):
         """Starts a pass: ``products`` over a pack of ``keys`` / ``widths`` (``pack_maps``) whose rows are the pixels of an
@@ -195,6 +222,14 @@ class FrameProducts:
         self.plan = kernels.frame_products_plan(self.n, specs, 0 if self.palette is None else self.palette.shape[0])
         self.workspace = torch.empty(max(kernels.frame_range_workspace_bytes(self.n) // 4, 1), dtype=torch.float32, device=device)
         self.streamer, self.in_flight, self.host = FrameStreamer(device), [], {}
+        if self.encode:
+            images = []
+            for (kind, width), (offset, _) in zip(self.kinds, self.plan[1]):
+                rgb = kind in (capi.FRAME_PALETTE, capi.FRAME_JET) or width == 3
+                images.append((self.shape[0], self.shape[1], 3 if rgb else 1, 16 if kind == capi.FRAME_U16 else 8, offset))
+            self.png_plan = kernels.png_plan(images)
+            self.png_workspace = torch.empty(max(self.png_plan[3], 1), dtype=torch.uint8, device=device)
+            self.file_streamer, self.files_in_flight, self.host_files = FrameStreamer(device), [], {}
 
     def add_frame(self, i, pack):
         """Frame ``i``'s pack ([H * W, columns] fp32 on the device) is complete on the current stream: its planes are computed
@@ -213,6 +248,36 @@ class FrameProducts:
         self.in_flight.append(int(i))
         if done is not None:
             self.host[self.in_flight.pop(0)] = done
+        if self.encode:
+            # the files in their worst-case places and, behind them, their lengths: one buffer, one copy
+            total, count = self.png_plan[2], len(self.names)
+            buf = torch.empty(total + 8 * max(count, 1), dtype=torch.uint8, device=self.device)
+            kernels.png_encode(out[:self.plan[2]], self.png_plan, out=buf[:total], sizes=buf[total:].view(torch.int64),
+                               workspace=self.png_workspace)
+            done = self.file_streamer.push(buf)
+            self.files_in_flight.append(int(i))
+            if done is not None:
+                self.host_files[self.files_in_flight.pop(0)] = done
+
+    def files(self, i):
+        """``{name: bytes}`` of frame ``i``: each product's complete PNG file (``encode=True``).  Waits for the copies up to frame ``i``
+        alone; a frame is handed out once."""
+        if not self.encode:
+            raise RuntimeError("FrameProducts.files: made without encode=True")
+        i = int(i)
+        while i not in self.host_files:
+            if not self.files_in_flight:
+                raise KeyError(f"FrameProducts.files({i}): no such frame in flight")
+            self.host_files[self.files_in_flight.pop(0)] = self.file_streamer.pop()
+        buf = self.host_files.pop(i)
+        total = self.png_plan[2]
+        sizes = buf[total:total + 8 * len(self.names)].view(np.int64)
+        out = {}
+        for name, (offset, capacity), size in zip(self.names, self.png_plan[1], sizes):
+            if not 0 < size <= capacity:
+                raise RuntimeError(f"FrameProducts.files({i}): {name!r} reports {int(size)} bytes, its buffer holds {capacity}")
+            out[name] = buf[offset:offset + int(size)].tobytes()
+        return out
 
     def images(self, i):
         """``{name: array}`` of frame ``i``: views of the frame's host bytes - uint8 [H, W] / [H, W, 3], uint16 [H, W].  Waits for

@@ -2123,3 +2123,68 @@ def jet_table():
     """JET[256, 3] uint8 (numpy) - the colour table of the JET products, from the library (csrc/jet_table.h)."""
     import numpy as np
     return np.frombuffer(bytes(_capi.lib().inerf_jet_table().contents), dtype=np.uint8).reshape(256, 3).copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PNG files on the device (csrc/png.hip): up to 16 planes - what ``frame_products`` wrote - become 16 complete PNG files in three
+# launches.  An image is ``(height, width, channels, bit_depth, src_offset[, filter])``: channels 1 | 3, bit_depth 8 | 16 (16 only
+# grey, little-endian in the plane), ``src_offset`` the plane's byte offset in ``src`` (a product's offset), ``filter``
+# _capi.PNG_FILTER_ADAPTIVE (default) or 0 .. 4
+# ---------------------------------------------------------------------------------------------------------------------
+def png_plan(images):
+    """Host only (``inerf_png_layout`` / ``inerf_png_workspace_bytes``; no device is touched): ``(args, files, total, workspace)`` -
+    an inerf_png_args with the images and their offsets filled in, ``files`` = [(offset, capacity)] per image (every offset a multiple
+    of 16; capacity: the worst-case file length), the byte count the output needs and the workspace's."""
+    images = list(images)
+    if len(images) > _capi.PNG_MAX_IMAGES:
+        raise ValueError(f"{len(images)} images: one call takes at most {_capi.PNG_MAX_IMAGES}")
+    a = _capi.PngArgs()
+    a.n_images = len(images)
+    for k, spec in enumerate(images):
+        im = a.images[k]
+        im.height, im.width, im.channels, im.bit_depth, im.src_offset = (int(v) for v in spec[:5])
+        im.filter = int(spec[5]) if len(spec) > 5 else _capi.PNG_FILTER_ADAPTIVE
+    total = int(_capi.lib().inerf_png_layout(C.byref(a)))
+    if total < 0:
+        _capi.check(total, "inerf_png_layout")
+    workspace = int(_capi.lib().inerf_png_workspace_bytes(C.byref(a)))
+    if workspace < 0:
+        _capi.check(workspace, "inerf_png_workspace_bytes")
+    files = [(int(a.images[k].dst_offset), int(a.images[k].dst_capacity)) for k in range(len(images))]
+    return a, files, total, workspace
+
+
+def png_encode(src, plan, out=None, sizes=None, workspace=None):
+    """The planes in ``src`` (a contiguous uint8 tensor on the device: ``frame_products``' output) as PNG files, in the three launches
+    of ``inerf_png_encode``.  ``plan``: what ``png_plan(images)`` returned; ``out``: a contiguous uint8 tensor of at least the plan's
+    total, ``sizes``: int64 [n_images], ``workspace``: a contiguous uint8 tensor of at least the plan's workspace (each allocated when
+    not given).  Returns ``(out, sizes)``: file k is ``out[offset_k : offset_k + sizes[k]]`` with ``offset_k`` = ``plan[1][k][0]``;
+    ``sizes`` lives on the device - nothing waits for it here."""
+    a, files, total, need = plan
+    if not (isinstance(src, torch.Tensor) and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()):
+        raise ValueError("src must be a contiguous 1-d uint8 tensor")
+    named = [("src", src)]
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=src.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= total):
+        raise ValueError(f"out must be a contiguous uint8 tensor of at least {total} bytes")
+    named.append(("out", out))
+    if sizes is None:
+        sizes = torch.zeros(max(a.n_images, 1), dtype=torch.int64, device=src.device)
+    elif not (isinstance(sizes, torch.Tensor) and sizes.dtype == torch.int64 and sizes.is_contiguous() and sizes.numel() >= a.n_images):
+        raise ValueError(f"sizes must be a contiguous int64 tensor of at least {a.n_images} values")
+    named.append(("sizes", sizes))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous uint8 tensor")
+    named.append(("workspace", workspace))
+    device = _eval_devices(named)
+    a.src, a.src_bytes = src.data_ptr(), src.numel()
+    a.dst, a.dst_bytes = out.data_ptr(), out.numel()
+    a.sizes = sizes.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_png_encode(C.byref(a), _stream(src))
+    _capi.check(rc, "inerf_png_encode")
+    return out, sizes

@@ -67,6 +67,10 @@ mirrors' ``render_path`` on the device (``frames.FrameProducts``, csrc/frame_vis
 and ``SSRTrainer.frame_products`` (SSR).  The SSR trainer's ``vis_deps`` / ``vis_entropys`` and its ``vis_depth_*`` / ``vis_entropy_*``
 files then need no imgviz at run time.
 
+``--inerf-frame-png`` (opt-in; implies ``--inerf-frame-products``) also encodes those images to PNG files on the device
+(``frames.FrameProducts(encode=True)``, csrc/png.hip): ``render_path(savedir=...)`` then writes the bytes it is handed - the same file
+names, the same pixels, other file bytes than the host encoder's.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -183,10 +187,11 @@ class _TrainerDraws:
 
 
 def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, losses=False, adam=False, draws=False, cluster_refresh=False,
-                        frame_products=False):
+                        frame_products=False, frame_png=False):
     """The object-level mirrors into ``namespace`` (a module's ``__dict__``): returns the names it bound."""
     from . import object_level
     cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
+    frame_products = frame_products or frame_png       # the files are encoded from the products' planes
     names = OBJECT_SYMBOLS + (OBJECT_OPTIONAL if with_render_path else ()) + ((LOSS_SYMBOL,) if losses else ())
     for name in names:
         namespace[name] = getattr(object_level, name)
@@ -211,12 +216,12 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
             extra["refresh"] = refresh.ClusterRefresh(manager_factory=factory)
         if frame_products:
             from . import frames
-            extra["products"] = frames.FrameProducts()
+            extra["products"] = frames.FrameProducts(encode=frame_png)
         namespace["render_path"] = functools.partial(object_level.render_path, cluster_manager_factory=factory, **extra)
     elif with_render_path and frame_products:
         import functools
         from . import frames
-        namespace["render_path"] = functools.partial(object_level.render_path, products=frames.FrameProducts())
+        namespace["render_path"] = functools.partial(object_level.render_path, products=frames.FrameProducts(encode=frame_png))
     return names
 
 
@@ -239,7 +244,7 @@ def rebind_eval():
 
 
 def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False, evaluate=False,
-               frame_products=False):
+               frame_products=False, frame_png=False):
     """The SSR mirrors into the (already imported) reference modules; returns {module name: [names bound]}."""
     from . import cluster as inerf_cluster, ssr
     cluster_fit = cluster_fit or (cluster_refresh and with_render_path)          # the refresh pass fits on the GPU
@@ -258,9 +263,9 @@ def rebind_ssr(with_render_path=False, cluster_fit=False, losses=False, adam=Fal
             from . import refresh
             trainer.SSRTrainer.cluster_refresh = refresh.ClusterRefresh(manager_factory=factory)
     bound["SSR.training.trainer.SSRTrainer"] = list(methods)
-    if with_render_path and frame_products:            # read by the mirror's render_path (ssr.SSRRenderMixin.frame_products is None)
+    if with_render_path and (frame_products or frame_png):      # read by the mirror's render_path (ssr.SSRRenderMixin.frame_products is None)
         from . import frames
-        trainer.SSRTrainer.frame_products = frames.FrameProducts()
+        trainer.SSRTrainer.frame_products = frames.FrameProducts(encode=frame_png)
         bound["SSR.training.trainer.SSRTrainer"].append("frame_products")
     for mod_name in SSR_MODULES:
         mod = sys.modules.get(mod_name)
@@ -321,7 +326,7 @@ def _object_eval_notice():
 
 
 def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False,
-            evaluate=False, frame_products=False):
+            evaluate=False, frame_products=False, frame_png=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
     script = os.path.abspath(script)
     kind = _kind(script)
@@ -334,7 +339,9 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
     mod.__file__ = script
     sys.modules[mod.__name__] = mod
     exec(body, mod.__dict__)
-    products = dict(frame_products=True) if frame_products else {}      # (only when given, as `evaluate` below)
+    products = dict(frame_products=True) if frame_products or frame_png else {}      # (only when given, as `evaluate` below)
+    if frame_png:
+        products["frame_png"] = True
     if kind == "object":
         mod.__dict__["__inerf_bound__"] = rebind_object_level(mod.__dict__, with_render_path, cluster_fit, losses, adam, draws, cluster_refresh,
                                                               **products)
@@ -379,6 +386,10 @@ def main(argv=None):
     frame_products = "--inerf-frame-products" in argv
     if frame_products:
         argv.remove("--inerf-frame-products")
+    frame_png = "--inerf-frame-png" in argv
+    if frame_png:
+        argv.remove("--inerf-frame-png")
+        frame_products = True                          # the files are encoded from the products' planes
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -397,6 +408,8 @@ def main(argv=None):
         extra["evaluate"] = True
     if frame_products:
         extra["frame_products"] = True
+    if frame_png:
+        extra["frame_png"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

@@ -452,8 +452,13 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     def finish(i, frame):
         if imaging:         # the five 8-bit images come from the device planes
             planes = products.images(i)
+            encoded = products.files(i) if getattr(products, "encode", False) else None      # PNG files made on the device
             for prefix in ("", "a", "s", "res", "acc"):
-                frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), planes[prefix])
+                if encoded is not None:
+                    with open(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), "wb") as fh:
+                        fh.write(encoded[prefix])
+                else:
+                    frames.write_png(os.path.join(savedir, "{}{:03d}.png".format(prefix, i)), planes[prefix])
         if slim:            # the frame holds the rgb and disp columns alone
             m = frames.unpack_frame(frame, widths[:2], keys[:2], (H, W))
             rgbs.append(m["rgb_map"]); disps.append(m["disp_map"])

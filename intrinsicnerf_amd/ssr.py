@@ -315,6 +315,11 @@ class SSRRenderMixin:
                 sample_labels.append(acc["sem"][-1][::2, ::2].reshape(-1, 1))
             if save_dir is not None:
                 w = lambda name, img: frames.write_png(os.path.join(save_dir, name.format(i)), img)
+                if img is not None and getattr(products, "encode", False):      # the files were encoded on the device: same names, same set
+                    for name, data in products.files(i).items():
+                        with open(os.path.join(save_dir, "{}_{:03d}.png".format(name, i)), "wb") as fh:
+                            fh.write(data)
+                    return
                 if img is not None:
                     for name in ("rgb", "albedo", "shading", "residual", "disp", "depth"):
                         w(name + "_{:03d}.png", img[name])
