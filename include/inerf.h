@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40025
+#define INERF_ABI_VERSION 40026
 
 /* error codes */
 #define INERF_OK              0
@@ -71,8 +71,21 @@ extern "C" {
  * every point, per tile of the probe (the same threshold, 7.5e3 unscaled, a factor 8.7 below f16's maximum; the probe's
  * activations are within 1e-3 of the exact ones, so the exact trunk cannot overflow on a point the probe did not flag).  The
  * exact trunk, whose tiles hold candidates of rays from anywhere in a sub-range, raises no flag of its own; the heads do, per point.
- * inerf_render_rays sets it wherever it sets the gate; INERF_PROBE=0 in the environment turns that off. */
+ * inerf_render_rays sets it wherever it sets the gate; INERF_PROBE=0 in the environment turns that off.
+ *
+ * THE MARGIN PER NETWORK.  kappa = 2^-6 is one constant for every network.  A caller that keeps a MARGIN STATE next to a packed blob -
+ * INERF_GATE_STATE_BYTES of device memory, 8-byte aligned, zeroed when the blob is packed and again whenever it is packed anew - and
+ * passes it (inerf_encode_mlp_margin `gate_state`, inerf_render_args.gate_state_coarse / gate_state_fine) gets that network's own:
+ * the exact trunk computes sigma of every candidate, so it measures r = |s - sigma| / S on each of them for free, and a launch uses
+ *   kappa = observed >= min_observed && isfinite(r_max) ? max(2^-9, 8 r_max) : 2^-6        (inerf_gate_kappa)
+ * fixed at its start for all of its sub-ranges.  While the margin in use is safe every point with positive density is a candidate, so
+ * the measured population is the population at risk; this is statistical evidence per network with the project's factor 8, not a
+ * per-point bound.  There is no upper clamp: a network with 8 r_max > 2^-6 gets the larger margin.  Nothing
+ * reads the state back, synchronises or allocates; a captured launch replays with whatever the state holds then.  One state serves
+ * one stream at a time.  NULL: the constant, and the launches of a library without the state, bit for bit.  Words of the state
+ * (written by the kernels alone): float r_max | float kappa_in_use | uint64 observed | uint32 launches | 3 reserved words. */
 #define INERF_FLAG_GATE_PROBE 64u
+#define INERF_GATE_STATE_BYTES 32
 
 /* arithmetic of the MLP GEMMs (inerf_net_desc.precision) */
 #define INERF_PREC_F32        0   /* v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation             */
@@ -177,6 +190,15 @@ int inerf_encode_mlp_chunked(const inerf_net_desc* net, const float* packed_weig
 int inerf_encode_mlp_probed(const inerf_net_desc* net, const float* packed_weights, const float* rays, const float* z_vals,
                             int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays,
                             void* workspace, int64_t workspace_bytes, float* probe_out, void* stream);
+/* The same with the probe's MARGIN STATE of this packed network (INERF_FLAG_GATE_PROBE above; device, INERF_GATE_STATE_BYTES, or NULL:
+ * inerf_encode_mlp_probed).  Used where the probe runs, ignored elsewhere. */
+int inerf_encode_mlp_margin(const inerf_net_desc* net, const float* packed_weights, const float* rays, const float* z_vals,
+                            int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays,
+                            void* workspace, int64_t workspace_bytes, float* probe_out, void* gate_state, void* stream);
+/* [host] The margin a launch would use for a state that holds (r_max, observed), and the number of listed points a network has to be
+ * measured on before its r_max is believed (INERF_PROBE_MIN_OBS in the environment overrides the built-in value). */
+float inerf_gate_kappa(float r_max, int64_t observed, int64_t min_observed);
+int64_t inerf_gate_min_observed(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Training: what autograd records for the network when the trainers call loss.backward()
@@ -414,6 +436,10 @@ typedef struct inerf_render_args {
     /* scratch */
     void*   workspace;
     int64_t workspace_bytes;
+    /* the probe's margin states (INERF_FLAG_GATE_PROBE; device, INERF_GATE_STATE_BYTES each, or NULL: the constant margin): of the
+     * network the coarse pass evaluates and of the one the fine pass evaluates - with packed_fine NULL, the coarse network's in both */
+    void* gate_state_coarse;
+    void* gate_state_fine;
 } inerf_render_args;
 
 /* Bytes of workspace inerf_render_rays needs for these sizes when the caller supplies none of the optional stage

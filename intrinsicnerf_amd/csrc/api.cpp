@@ -131,9 +131,9 @@ static int render_impl(const inerf_render_args* a, const inerf_draw_args* d, voi
     float* raw_c = a->raw_coarse ? a->raw_coarse : f(p.raw_c);
     // the coarse net never emits the endpoint feature (trainer.py:751-755: endpoint_feat=False)
     const uint32_t mlp_flags = a->flags & ~kGateFlags;
-    rc = inerf_encode_mlp_chunked(&a->net, a->packed_coarse, a->rays, z_c, n, sc,
-                                  (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr || drawn_noise), raw_c, a->status,
-                                  a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
+    rc = inerf_encode_mlp_margin(&a->net, a->packed_coarse, a->rays, z_c, n, sc,
+                                 (mlp_flags & ~INERF_FLAG_ENDPOINT) | gate_flag(a->raw_coarse != nullptr, a->noise_coarse != nullptr || drawn_noise), raw_c, a->status,
+                                 a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, nullptr, a->gate_state_coarse, stream);
     if (rc) return rc;
     inerf_composite_out oc = a->coarse;
     oc.feat = nullptr;
@@ -152,8 +152,8 @@ static int render_impl(const inerf_render_args* a, const inerf_draw_args* d, voi
     if (rc) return rc;
     float* raw_f = a->raw_fine ? a->raw_fine : f(p.raw_f);
     const float* w_fine = a->packed_fine ? a->packed_fine : a->packed_coarse;   // run_nerf.py:506
-    rc = inerf_encode_mlp_chunked(&a->net, w_fine, a->rays, z_f, n, p.s_f, mlp_flags | gate_flag(a->raw_fine != nullptr, a->noise_fine != nullptr || drawn_noise), raw_f,
-                                  a->status, a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, stream);
+    rc = inerf_encode_mlp_margin(&a->net, w_fine, a->rays, z_f, n, p.s_f, mlp_flags | gate_flag(a->raw_fine != nullptr, a->noise_fine != nullptr || drawn_noise), raw_f,
+                                 a->status, a->status_rays, ws + p.mlp_ws, p.mlp_ws_bytes, nullptr, a->gate_state_fine, stream);
     if (rc) return rc;
     const bool ep = ssr && (a->flags & INERF_FLAG_ENDPOINT);
     inerf_composite_out of = a->fine;

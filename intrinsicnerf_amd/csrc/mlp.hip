@@ -406,7 +406,8 @@ int launch_mlp_f32(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream)
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch = nullptr, int64_t status_rays = 0, void* gate_ws = nullptr, float* probe_out = nullptr);
+                           float* sem_scratch = nullptr, int64_t status_rays = 0, void* gate_ws = nullptr, float* probe_out = nullptr,
+                           void* gate_state = nullptr);
 
 // workspace of a launch: the kernels' scratch (sem_scratch_bytes), then - 256-byte aligned - the density gate's buffers
 static bool gated(const inerf_net_desc& net, uint32_t flags) { return (flags & INERF_FLAG_GATE_COLOUR) && inerf::mlp_gate_applies(net, flags); }
@@ -454,6 +455,18 @@ extern "C" int inerf_encode_mlp_probed(const inerf_net_desc* net, const float* p
                            probe_out);
 }
 
+extern "C" int inerf_encode_mlp_margin(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
+                                       int n_samples, uint32_t flags, float* raw_out, int32_t* status, int64_t status_rays, void* workspace,
+                                       int64_t workspace_bytes, float* probe_out, void* gate_state, void* stream) {
+    if (!net || !inerf::net_supported(*net) || n_rays < 0 || n_samples < 1) return INERF_E_INVALID;
+    if (reinterpret_cast<uintptr_t>(gate_state) & 7) return INERF_E_INVALID;      // (the 64-bit count)
+    const int64_t need = workspace_need(*net, n_rays, n_samples, flags), scratch = scratch_bytes(*net, n_rays, n_samples, flags);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return INERF_E_WORKSPACE;
+    return encode_mlp_impl(net, packed, rays, z, n_rays, n_samples, flags, raw_out, nullptr, nullptr, status, stream,
+                           scratch > 0 ? static_cast<float*>(workspace) : nullptr, status_rays, need > scratch ? static_cast<char*>(workspace) + scratch : nullptr,
+                           probe_out, gate_state);
+}
+
 extern "C" int inerf_encode_mlp(const inerf_net_desc* net, const float* packed, const float* rays, const float* z,
                                 int64_t n_rays, int n_samples, uint32_t flags, float* raw_out, int32_t* status,
                                 void* stream) {
@@ -489,7 +502,7 @@ extern "C" int inerf_encode_mlp_train(const inerf_net_desc* net, const float* pa
 
 static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const float* rays, const float* z, int64_t n_rays,
                            int n_samples, uint32_t flags, float* raw_out, float* save, float* act_max, int32_t* status, void* stream,
-                           float* sem_scratch, int64_t status_rays, void* gate_ws, float* probe_out) {
+                           float* sem_scratch, int64_t status_rays, void* gate_ws, float* probe_out, void* gate_state) {
     using namespace inerf;
     if ((flags & INERF_FLAG_GATE_PROBE) && !(flags & INERF_FLAG_GATE_COLOUR)) return INERF_E_INVALID;      // the probe is a form of the gate
     if (net && n_rays == 0) return net_supported(*net) ? INERF_OK : INERF_E_UNSUPPORTED;      // empty batch: pointers may be null
@@ -518,6 +531,7 @@ static int encode_mlp_impl(const inerf_net_desc* net, const float* packed, const
     if (!save && gated(*net, flags)) {      // colour heads only on points with positive density (include/inerf.h INERF_FLAG_GATE_COLOUR)
         if (!gate_ws) return INERF_E_WORKSPACE;
         p.probe_out = probe_out;
+        p.gate_state = static_cast<GateMargin*>(gate_state);      // (used with the probe alone)
         return launch_mlp_f16x3_gated(p, n_rays, gate_ws, (flags & INERF_FLAG_GATE_PROBE) != 0, (hipStream_t)stream);
     }
     return net->precision == INERF_PREC_F16X3 ? launch_mlp_f16x3(p, n_points, ssr, (hipStream_t)stream)

@@ -8,6 +8,35 @@
 
 namespace inerf {
 
+// The probe's cull margin.  The probe culls a point when s < -kappa S.  kappa = 8 x the largest r = |s - sigma| / S: as ONE
+// constant, kProbeKappa, the power of two above 8 x the worst r of the networks it was fitted to (profiles/gate_probe_margin.txt) - or, with a
+// GateMargin state, 8 x the largest r the listed trunk has measured on THIS packed network's own candidates, once it has seen enough of them.
+constexpr float kProbeKappa = 0x1p-6f;              // before a network has been observed, and wherever no state is given
+constexpr float kProbeKappaFloor = 0x1p-9f;         // the smallest 8 r of the project's networks (1.56e-3), rounded up to a power of two
+constexpr float kProbeFactor = 8.0f;
+// Listed points measured before r_max is believed.  On the bench frame r over all listed points of a pass is within 2 x r over its first n
+// from n = 2^10 on (profiles/gate_margin_bench.txt section 2); 2^20 is deliberately more: within 1.13 x in both passes, more than any
+// small launch lists (those stay on the constant), and reached inside the first sub-range launch of a frame.
+constexpr unsigned long long kProbeMinObserved = 1ull << 20;
+
+// INERF_GATE_STATE_BYTES of include/inerf.h: device memory, zero-initialised, one per packed blob.  Written by the kernels alone.
+struct GateMargin {
+    float r_max;                    // >= 0: the largest finite |s - sigma| / S of a listed point (atomicMax on its bits)
+    float kappa_in_use;             // the margin of the launch in flight (k_gate_margin_begin)
+    unsigned long long observed;    // listed points measured so far
+    unsigned int launches;          // launches that have used this state
+    unsigned int reserved[3];
+};
+static_assert(sizeof(GateMargin) == 32, "INERF_GATE_STATE_BYTES");
+
+// the one statement of the rule (host: inerf_gate_kappa, which the CPU tests pin; device: k_gate_margin_begin)
+__host__ __device__ inline float gate_kappa(float r_max, unsigned long long observed, unsigned long long min_observed) {
+    const bool finite = r_max - r_max == 0.0f;      // neither NaN nor an infinity
+    if (!(observed >= min_observed) || !finite) return kProbeKappa;
+    const float k = kProbeFactor * r_max;
+    return k > kProbeKappaFloor ? k : kProbeKappaFloor;
+}
+
 struct MlpParams {
     const float* wts;       // packed blob
     const float* rays;      // [N,11]
@@ -43,12 +72,16 @@ struct MlpParams {
     float grid_dist;                // occ = 1 - exp(-relu(sigma) * grid_dist)
     float* occ;                     // [n_points]
     float* sigma_out;               // [n_points] or nullptr
+    // the probe's cull margin per packed network (appended likewise): nullptr = the constant kProbeKappa and no (s, S) list
+    GateMargin* gate_state;         // caller-owned, zeroed when the network is packed; the listed trunk measures |s - sigma| / S into it
+    float* cand_ss;                 // (s, S) of the probe per candidate, in the order of cand_idx
 };
 
 struct GatePlan {
     int64_t rays_per_sub, n_sub;        // sub-ranges of whole rays
     int64_t idx_off, count_off, bytes;  // workspace: records at 0, point indices, one counter per sub-range
     int64_t cand_off, cand_count_off;   // ... the probe's candidate list and its counter per sub-range
+    int64_t cand_ss_off;                // ... and the candidates' (s, S), 8 B per point of a sub-range (read only with a GateMargin state)
 };
 GatePlan mlp_gate_plan(int64_t n_rays, int n_samples);
 bool mlp_gate_applies(const inerf_net_desc& net, uint32_t flags);      // which launches the flag changes anything for

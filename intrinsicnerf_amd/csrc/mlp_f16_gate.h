@@ -151,9 +151,12 @@ __device__ __forceinline__ void post_count(_Float16* ldst, int g, unsigned kept,
 // point[h] when keep[h]; kept[h] = the ballot, posted).  The eight counts meet in pad words 0..7, thread 0 reserves the tile's contiguous range
 // with ONE atomicAdd on `counter` (first slot: pad word 8), every kept point's index goes into `list`.  Returns this wave's first slot
 // (<= the launch's points - this wave's kept points: inside the buffers).  Two barriers: every wave's rows are written behind the first.
+// ss_list (the probe with a GateMargin state; else nullptr, a uniform branch): the kept point's (s, S) = (s[h], big_s[h]) into ss_list[slot], for
+// the listed trunk to hold against the exact sigma.
 template <int kGroups>
 __device__ __forceinline__ int reserve_slots(_Float16* ldst, unsigned int* counter, int* list, const bool (&keep)[kGroups], const unsigned (&kept)[kGroups],
-                                             const int (&point)[kGroups], int wave, int lane_t, int tid) {
+                                             const int (&point)[kGroups], int wave, int lane_t, int tid, float* ss_list = nullptr,
+                                             const float* s = nullptr, const float* big_s = nullptr) {
     __syncthreads();                           // the eight counts are there
     int before = 0, total = 0;
 #pragma unroll
@@ -168,7 +171,11 @@ __device__ __forceinline__ int reserve_slots(_Float16* ldst, unsigned int* count
     int slot = slot0;
 #pragma unroll
     for (int h = 0; h < kGroups; ++h) {
-        if (keep[h]) list[slot + __popc(kept[h] & ((1u << lane_t) - 1u))] = point[h];
+        if (keep[h]) {
+            const int at = slot + __popc(kept[h] & ((1u << lane_t) - 1u));
+            list[at] = point[h];
+            if (ss_list) *reinterpret_cast<float2*>(ss_list + 2 * (size_t)at) = float2{s[h], big_s[h]};
+        }
         slot += __popc(kept[h]);
     }
     return slot0;

@@ -38,6 +38,7 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
     auto frag64 = [&](const GemmSlot& s, int kbt) { return (s.w + wave * kbt * 2 * 2 * 256) * 4; };
     WidePreH<2> pre;
     prefetch_w<2, 4096, 2048, 1>(pre, wb, frag64(L.trunk[0], 4));
+    const float kappa = probe_kappa(p);          // the margin of this launch
 
     for (int tile = blockIdx.x; tile < p.n_tiles; tile += gridDim.x) {
         int lane_t = tid;                         // (laundered per tile, like the eight-wave form's)
@@ -72,14 +73,16 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
         // (group 2 wave + h is wave 2 wave + h of the eight-wave form: the same counts in the same pad words, the list in point order)
         bool keep[2];
         unsigned kept[2];
+        float s_row[2], big_s_row[2];              // lanes 0..15: the groups' (s, S)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int pt16 = tile * kPtsT + 32 * wave + 16 * h;
             const _Float16* const xs_g = ldst + (32 * wave + 16 * h + (lane_t & 15)) * kRowD + 8 * (lane_t >> 4);
-            float sigma, scale;                    // lanes 0..15: the group's points
+            float& sigma = s_row[h];
+            float& scale = big_s_row[h];
             skinny_probe_h<8>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t, sigma, scale);
             const bool valid = lane_t < 16 && pt16 + lane_t < p.n_points;
-            keep[h] = valid && !(sigma < -kProbeKappa * scale);
+            keep[h] = valid && !(sigma < -kappa * scale);
             kept[h] = __builtin_amdgcn_readfirstlane((unsigned)__ballot(keep[h]));
             store_sigma_rows(p, pt16, sigma, lane_t);
             if (p.probe_out && valid) {            // tests: (s, S) per point
@@ -91,7 +94,7 @@ __device__ __forceinline__ void mlp_gate_probe_wg2_tiles(const MlpParams& p) {
         post_count(ldst, 2 * wave + 1, kept[1], lane_t);     // longer - profiles/gate_dedup_bench.txt)
         const int pt32 = tile * kPtsT + 32 * wave;
         const int point[2] = {pt32 + lane_t, pt32 + 16 + lane_t};
-        reserve_slots<2>(ldst, p.cand_count, p.cand_idx, keep, kept, point, wave, lane_t, tid);
+        reserve_slots<2>(ldst, p.cand_count, p.cand_idx, keep, kept, point, wave, lane_t, tid, p.cand_ss, s_row, big_s_row);
         flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
         __syncthreads();                           // the rows and the pad words are read: the next tile's encode and parking may overwrite them
     }

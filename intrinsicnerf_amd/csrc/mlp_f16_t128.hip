@@ -104,8 +104,15 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 //               occ[gp] = 1 - exp(-relu(sigma) grid_dist) and, when asked for, sigma_out[gp] - no raw rows, no records, no atomics.
 enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3, kGridTrunk = 4 };
 constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
-// The probe's margin: the smallest power of two >= 8 x the largest |s - sigma| / S measured on the GPU (profiles/gate_probe_margin.txt).
-constexpr float kProbeKappa = 0x1p-6f;
+// (the probe's margin, kProbeKappa or a GateMargin state's kappa_in_use: mlp_common.h)
+
+// The margin of the launch in flight: p.gate_state's kappa_in_use (written by k_gate_margin_begin in front of the launch's first probe kernel
+// on the stream, the same for every sub-range), read once per kernel like the counts; without a state the constant.
+__device__ __forceinline__ float probe_kappa(const MlpParams& p) {
+    if (!p.gate_state) return kProbeKappa;
+    const unsigned bits = *reinterpret_cast<const volatile unsigned*>(&p.gate_state->kappa_in_use);
+    return __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_readfirstlane((int)bits));
+}
 
 }  // namespace inerf
 #include "mlp_f16_gate.h"       // the pieces the gate's kernels share: encoder, parking, probe trunk, raw rows, slots
@@ -157,6 +164,12 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         n_rec = __builtin_amdgcn_readfirstlane((int)*reinterpret_cast<const volatile unsigned*>(p.cand_count));
         n_rec = n_rec < p.n_points ? n_rec : p.n_points;
     }
+    float kappa = kProbeKappa;                    // probe: the margin of this launch
+    if constexpr (kMode == kGateProbe) kappa = probe_kappa(p);
+    // listed trunk with a GateMargin state: r = |s - sigma| / S of every listed point - this lane's running maximum (lanes 0..15 hold rows)
+    // and this wave's count of measured rows, across the tile loop; they leave at kernel exit
+    float r_seen = 0.0f;
+    int n_seen = 0;
     const int n_tiles = kMode == kGateHeads || kListed ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
     auto pad_of = [&](int r) { return pad_words(ldst, r); };      // (gated heads: the point's range flags)
     float amax = 0.0f;                            // running maxima of |scaled value| (encoder inputs / layer outputs): the f16 range guard
@@ -424,13 +437,23 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             if constexpr (kMode == kGateProbe) skinny_probe_h<8>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t, sigma, scale);
             else sigma = skinny_gemm_h<8, kPlaneT>(wb, L.alpha.w * 4, L.alpha.b * 4, (L.alpha.b + 16) * 4, xs_g, lane_t)[0];
             const bool valid = lane_t < 16 && pt16 + lane_t < (kListed ? n_rec : p.n_points);
-            const bool keep[1] = {valid && (kMode == kGateProbe ? !(sigma < -kProbeKappa * scale) : !(sigma <= 0.0f))};
+            const bool keep[1] = {valid && (kMode == kGateProbe ? !(sigma < -kappa * scale) : !(sigma <= 0.0f))};
             const unsigned kept[1] = {(unsigned)__builtin_amdgcn_readfirstlane((unsigned)__ballot(keep[0]))};
             post_count(ldst, wave, kept[0], lane_t);
             int my_point[1] = {pt16 + lane_t};         // the row's point within the sub-range
             if constexpr (kListed) {                   // exact sigma into the candidate's raw row, whose other ten channels the probe zeroed
                 my_point[0] = p.cand_idx[valid ? pt16 + lane_t : 0];
                 if (valid) __builtin_nontemporal_store(sigma, p.raw + (size_t)my_point[0] * p.channels + 3);
+                if (p.gate_state) {                    // (uniform) the probe's error on this row, in correctly rounded operations; a NaN density,
+                    bool seen = false;                 // an infinite s or S == 0 is not counted and cannot poison the maximum
+                    if (valid) {
+                        const float2 ss = *reinterpret_cast<const float2*>(p.cand_ss + 2 * (size_t)(pt16 + lane_t));
+                        const float e = __fdiv_rn(fabsf(__fsub_rn(ss.x, sigma)), ss.y);
+                        seen = ss.y > 0.0f && e - e == 0.0f;
+                        if (seen) r_seen = fmaxf(r_seen, e);
+                    }
+                    n_seen += __popcll(__ballot(seen));
+                }
             } else {
                 store_sigma_rows(p, pt16, sigma, lane_t);
             }
@@ -439,8 +462,9 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                     p.probe_out[2 * (size_t)(pt16 + lane_t)] = sigma;
                     p.probe_out[2 * (size_t)(pt16 + lane_t) + 1] = scale;
                 }
+            const float s_row[1] = {sigma}, big_s_row[1] = {scale};
             const int slot0 = reserve_slots<1>(ldst, kMode == kGateProbe ? p.cand_count : p.gate_count, kMode == kGateProbe ? p.cand_idx : p.gate_idx,
-                                               keep, kept, my_point, wave, lane_t, tid);
+                                               keep, kept, my_point, wave, lane_t, tid, kMode == kGateProbe ? p.cand_ss : nullptr, s_row, big_s_row);
             if constexpr (kMode == kGateTrunk) {
                 int slot = slot0;
                 for (unsigned m = kept[0]; m != 0u; m &= m - 1u, ++slot) {      // one 1 KB record per instruction: lane = sixteen-byte piece of the row, hi plane | lo plane
@@ -708,6 +732,24 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         // (the next tile's encode writes bytes 0..127 and 512..575 of the rows, both planes: clear of the exchange area (hi plane, bytes
         // 128..255) and of the staging rows (lo plane, bytes 256..299) this tile's last readers may still be in)
     }
+    if constexpr (kListed) {
+        if (p.gate_state) {      // (uniform) one atomicMax per wave, one 64-bit atomicAdd per workgroup (the counts meet in pad words 0..7: every
+                                 // tile's last readers of them are behind its closing barrier)
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) r_seen = fmaxf(r_seen, __shfl_xor(r_seen, o));
+            if (lane == 0) {
+                if (r_seen > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&p.gate_state->r_max), __builtin_bit_cast(unsigned int, r_seen));
+                pad_words(ldst, wave)[0] = n_seen;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned long long total = 0;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) total += (unsigned long long)pad_words(ldst, g)[0];
+                if (total > 0) atomicAdd(&p.gate_state->observed, total);
+            }
+        }
+    }
     if (kSave && p.act_max) {
         float m = split_upper_bound(amax, amax2) * (1.0f / kActScale);
 #pragma unroll
@@ -762,11 +804,29 @@ GatePlan mlp_gate_plan(int64_t n_rays, int n_samples) {
     // (the probe's candidate list and counters come behind the budgeted part: the sub-ranges are the same with and without the probe)
     g.cand_off = g.count_off + up(g.n_sub * 4);
     g.cand_count_off = g.cand_off + up(pts * 4);
-    g.bytes = g.cand_count_off + up(g.n_sub * 4);
+    g.cand_ss_off = g.cand_count_off + up(g.n_sub * 4);
+    g.bytes = g.cand_ss_off + up(pts * 8);
     return g;
 }
 
-// `probe` (INERF_FLAG_GATE_PROBE): probe kernel -> listed trunk -> heads per sub-range instead of trunk -> heads.
+// kProbeMinObserved, or INERF_PROBE_MIN_OBS from the environment (tests)
+static unsigned long long probe_min_observed() {
+    if (const char* e = getenv("INERF_PROBE_MIN_OBS")) {
+        const double v = atof(e);
+        if (v >= 0.0) return v < 1.8e19 ? (unsigned long long)v : ~0ull;
+    }
+    return kProbeMinObserved;
+}
+
+// One thread in front of a launch's first probe kernel: the margin every sub-range of the launch uses.  What the listed trunks of this launch
+// measure moves r_max and observed, not kappa_in_use.
+__global__ void k_gate_margin_begin(GateMargin* st, unsigned long long min_observed) {
+    st->kappa_in_use = gate_kappa(st->r_max, st->observed, min_observed);
+    st->launches += 1u;
+}
+
+// `probe` (INERF_FLAG_GATE_PROBE): probe kernel -> listed trunk -> heads per sub-range instead of trunk -> heads.  With p0.gate_state the probe's
+// margin is that state's (k_gate_margin_begin), the probe lists its candidates' (s, S) and the listed trunk measures them against the exact sigma.
 int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, bool probe, hipStream_t stream) {
     const GatePlan g = mlp_gate_plan(n_rays, p0.n_samples);
     char* const ws = static_cast<char*>(gate_ws);
@@ -789,6 +849,8 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
     // the probe's form: two four-wave workgroups per CU (mlp_f16_probe.h); INERF_PROBE_WG=1: the eight-wave workgroup (the same bits)
     const char* const wg_env = getenv("INERF_PROBE_WG");
     const bool probe_wg2 = !(wg_env && wg_env[0] == '1');
+    GateMargin* const margin = probe ? p0.gate_state : nullptr;
+    if (margin) hipLaunchKernelGGL(k_gate_margin_begin, dim3(1), dim3(1), 0, stream, margin, probe_min_observed());
     for (int64_t s = 0; s < g.n_sub; ++s) {
         const int64_t r0 = s * g.rays_per_sub, nr = n_rays - r0 < g.rays_per_sub ? n_rays - r0 : g.rays_per_sub;
         MlpParams p = p0;
@@ -803,6 +865,8 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         p.gate_count = counts + s;
         p.cand_idx = reinterpret_cast<int*>(ws + g.cand_off);
         p.cand_count = cand_counts + s;
+        p.gate_state = margin;
+        p.cand_ss = margin ? reinterpret_cast<float*>(ws + g.cand_ss_off) : nullptr;
         if (p.probe_out) p.probe_out = p0.probe_out + 2 * r0 * p0.n_samples;
         const int grid = p.n_tiles < device_cus() ? p.n_tiles : device_cus();
         if (probe) {
@@ -831,10 +895,27 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         fprintf(stderr, "inerf gate: %lld rays x %d samples in %lld sub-launches, %llu of %lld points survive (%.4f)", (long long)n_rays,
                 p0.n_samples, (long long)g.n_sub, kept, (long long)(n_rays * p0.n_samples), (double)kept / pts);
         if (probe) fprintf(stderr, ", %llu are the probe's candidates (%.4f)", cand, (double)cand / pts);
+        if (margin) {
+            GateMargin m{};
+            if (e == hipSuccess) e = hipMemcpy(&m, margin, sizeof m, hipMemcpyDeviceToHost);
+            fprintf(stderr, ", margin %.6g (r_max %.6g over %llu listed points, launch %u)", (double)m.kappa_in_use, (double)m.r_max, m.observed, m.launches);
+        }
         fprintf(stderr, "\n");
     }
     return record(e);
 }
+
+}  // namespace inerf
+
+extern "C" float inerf_gate_kappa(float r_max, int64_t observed, int64_t min_observed) {
+    return inerf::gate_kappa(r_max, observed < 0 ? 0ull : (unsigned long long)observed, min_observed < 0 ? 0ull : (unsigned long long)min_observed);
+}
+extern "C" int64_t inerf_gate_min_observed(void) {
+    const unsigned long long v = inerf::probe_min_observed();
+    return v > (unsigned long long)INT64_MAX ? INT64_MAX : (int64_t)v;
+}
+
+namespace inerf {
 
 // The occupancy grid's launch: like the gated trunk's - one eight-wave workgroup per CU with the parked encoding's extension area, persistent over the tiles.
 int launch_grid_trunk_f16x3(MlpParams& p, int64_t n_points, bool ssr, hipStream_t stream) {

@@ -817,12 +817,31 @@ def with_f32_fallback(desc, run):
         return run(d32)
 
 
-def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_colour=False, status_rays=0, gate_probe=False, probe_out=None):
+def gate_margin(state):
+    """{r_max, observed, kappa_in_use, launches} of a gate-probe margin state (``packing.gate_state_of``; include/inerf.h
+    INERF_FLAG_GATE_PROBE).  Synchronises: for logs and tests."""
+    w = state.detach().cpu()
+    f = w.view(torch.float32)
+    return dict(r_max=float(f[0]), kappa_in_use=float(f[1]), observed=int(w.view(torch.int64)[1]), launches=int(w[4]) & 0xFFFFFFFF)
+
+
+def _gate_state_ptr(state, like):
+    if state is None:
+        return None
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.device == like.device and state.dtype == torch.int32
+            and state.numel() == 8 and state.is_contiguous()):
+        raise ValueError("gate_state must be a contiguous int32[8] tensor on the rays' device (packing.gate_state_of)")
+    return C.c_void_p(state.data_ptr())
+
+
+def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_colour=False, status_rays=0, gate_probe=False, probe_out=None,
+               gate_state=None):
     """raw[N,S,CH]: fused encoding + MLP (run_network + NeRF.forward).
 
     ``status``: optional int32[1] device tensor that collects INERF_STATUS_* bits (PREC_F16X3 range check); with ``status_rays`` > 0
     one word per that many rays.  ``gate_colour``: INERF_FLAG_GATE_COLOUR (include/inerf.h) - rows with sigma <= 0 carry zero colours.
-    ``gate_probe``: INERF_FLAG_GATE_PROBE on top of it; ``probe_out`` (tests): a float32 [N * S, 2] device tensor for the probe's (s, S)."""
+    ``gate_probe``: INERF_FLAG_GATE_PROBE on top of it; ``probe_out`` (tests): a float32 [N * S, 2] device tensor for the probe's (s, S);
+    ``gate_state``: the probe's margin state of ``packed`` (``packing.gate_state_of``) - None: the constant margin."""
     rays = _dev(rays, "rays", (None, RAY_FLOATS))
     z_vals = _dev(z_vals, "z_vals", (rays.shape[0], None))
     packed = _dev(packed, "packed weights", (None,))
@@ -837,11 +856,12 @@ def encode_mlp(desc, packed, rays, z_vals, endpoint=False, status=None, gate_col
         if ws_bytes < 0:
             _capi.check(ws_bytes, "inerf_encode_mlp_workspace_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=rays.device) if ws_bytes > 0 else None
-        rc = _capi.lib().inerf_encode_mlp_probed(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
+        rc = _capi.lib().inerf_encode_mlp_margin(desc, _ptr(packed), _ptr(rays), _ptr(z_vals), n, s, flags, _ptr(raw),
                                                  None if status is None else C.c_void_p(status.data_ptr()), int(status_rays),
                                                  None if ws is None else C.c_void_p(ws.data_ptr()), ws_bytes,
-                                                 None if probe_out is None else C.c_void_p(probe_out.data_ptr()), _stream(rays))
-    _capi.check(rc, "inerf_encode_mlp_probed")
+                                                 None if probe_out is None else C.c_void_p(probe_out.data_ptr()),
+                                                 _gate_state_ptr(gate_state, rays), _stream(rays))
+    _capi.check(rc, "inerf_encode_mlp_margin")
     return raw
 
 
@@ -1020,6 +1040,10 @@ def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_impor
     Returns a dict with ``{rgb,disp,acc,depth,albedo,shading,residual[,sem]}_{coarse,fine}``, ``z_std``
     and, on request, ``raw_*`` / stage tensors (``z_coarse, weights_coarse, z_samples, z_fine,
     weights_fine``).  Everything is enqueued on the current stream; nothing synchronises.
+
+    The gate probe's cull margin adapts to each network (include/inerf.h INERF_FLAG_GATE_PROBE): the margin state of a blob is
+    ``packing.gate_state_of(blob)``, so it is remembered for as long as the same blob tensor is passed.  INERF_PROBE_ADAPT=0: no state,
+    the constant margin.
     """
     L = _capi.lib()
     rays = _dev(rays, "rays", (None, RAY_FLOATS))
@@ -1092,6 +1116,11 @@ def render_rays_fused(desc, packed_coarse, packed_fine, rays, n_samples, n_impor
         _capi.check(int(ws_bytes), "inerf_render_workspace_bytes")
     ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=rays.device)
     args.workspace, args.workspace_bytes = ws.data_ptr(), int(ws_bytes)
+    if os.environ.get("INERF_PROBE_ADAPT", "1")[:1] != "0":
+        from . import packing
+        st_c = packing.gate_state_of(packed_coarse)
+        st_f = st_c if packed_fine is None else packing.gate_state_of(packed_fine)
+        args.gate_state_coarse, args.gate_state_fine = _gate_state_ptr(st_c, rays), _gate_state_ptr(st_f, rays)
     if desc.precision == _capi.PREC_F16X3:
         # caller checks it (check_f16_range) when it next synchronises; inside a chunked_status() block: one word per chunk of rays
         words = -(-n // _status_rays) if (_status_rays > 0 and n > _status_rays) else 1

@@ -61,7 +61,25 @@ def pack_state_dict(desc, state_dict):
 
 
 class _Entry:
-    __slots__ = ("versions", "blob")
+    __slots__ = ("versions", "blob", "gate_state")
+
+
+GATE_STATE_WORDS = 8        # INERF_GATE_STATE_BYTES / 4 (include/inerf.h): float r_max | float kappa_in_use | uint64 observed | uint32 launches | 3 reserved
+
+
+def gate_state_of(blob):
+    """The gate probe's margin state of a packed device blob (include/inerf.h INERF_FLAG_GATE_PROBE): eight int32 words
+    of device memory, zeroed, that live and die with the blob TENSOR - made when the blob is packed (``packed_for_module``: a repack
+    starts a new one from zero) or, for a bare blob, the first time it is asked for.  The kernels alone write it
+    (``kernels.gate_margin`` reads it).  None for a blob that is not on a HIP device.  Whoever overwrites a blob's storage in place
+    with other weights must zero its state as well."""
+    if not blob.is_cuda:
+        return None
+    st = getattr(blob, "_inerf_gate_state", None)
+    if st is None:
+        st = torch.zeros(GATE_STATE_WORDS, dtype=torch.int32, device=blob.device)
+        blob._inerf_gate_state = st
+    return st
 
 
 _cache = weakref.WeakKeyDictionary()      # module -> {precision: _Entry}
@@ -95,6 +113,7 @@ def packed_for_module(module, desc, device):
                 ent.blob = device_packer_f32(desc, params[0].device)(dict(module.named_parameters()))
         else:
             ent.blob = pack_state_dict(desc, module.state_dict()).to(device)
+        ent.gate_state = gate_state_of(ent.blob)        # a new blob: the probe's margin starts from the constant again
         per_module[desc.precision] = ent
     return ent.blob
 
