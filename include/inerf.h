@@ -30,7 +30,7 @@ extern "C" {
 #define INERF_VERSION_MINOR 2
 /* Bumped whenever a struct layout, an argument list or the packed-weight format of this header changes; bindings
  * compare it with inerf_abi_version() of the library they loaded (a stale .so then fails loudly, not silently). */
-#define INERF_ABI_VERSION 40026
+#define INERF_ABI_VERSION 40027
 
 /* error codes */
 #define INERF_OK              0
@@ -1500,6 +1500,93 @@ int inerf_png_encode(const inerf_png_args* args, void* stream);
  * broken by the symbol index.  INERF_E_INVALID: NULL pointers, n outside 1 .. 288, limit outside 1 .. 15, more used symbols than
  * 2^limit, counts whose sum exceeds 32 bits. */
 int inerf_png_code_lengths(const uint32_t* freq, int n, int limit, unsigned char* lengths);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frame movies on the device (csrc/jpeg.hip, csrc/jpeg_tables.h): up to 16 image planes - exactly what inerf_frame_products
+ * writes - become 16 baseline JPEG files, each appended as one AVI chunk to a device-resident arena: the `movi` payload of a
+ * Motion-JPEG AVI file, verbatim.  Replaces imageio.mimwrite / cv2.VideoWriter at the end of the reference's render passes
+ * (object_level/run_nerf.py:822, :1051-1052; SSR/training/trainer.py:1088-1093, :1169-1174; gui.py, gui_obj.py,
+ * video_generator.py, which names MJPG / .avi as its own alternative container).
+ * FILE      SOI, JFIF APP0 (1.01, no units, 1 : 1), DQT (one for grey, two for colour), SOF0 (8 bits; components 1 .. 3, sampling
+ *           1 x 1: 4:4:4), DHT (the T.81 Annex K tables: DC then AC, luminance, then chrominance for colour), DRI, SOS, the
+ *           entropy-coded data, EOI.  Everything before the data is the HEADER: 334 bytes for grey, 629 for colour, the same for
+ *           every frame of a stream; inerf_jpeg_header builds it once on the host and the caller keeps a device copy.
+ * TABLES    Annex K luminance / chrominance scaled by quality 1 .. 100 with libjpeg's rule: s = q < 50 ? 5000 / q : 200 - 2 q,
+ *           t = clamp((base * s + 50) / 100, 1, 255).  The kernel reads them from the header's DQT segments.
+ * SAMPLES   grey: the plane.  Colour: the plane is RGB; Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *           Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16.
+ *           A width or height that is no multiple of 8 repeats the last column / row.
+ * DCT       p = sample - 128; M[u][x] = round(8192 a(u) cos((2 x + 1) u pi / 16)), a(0) = sqrt(1 / 8), a(u) = 1 / 2 (tabulated);
+ *           rows: t[y][u] = (sum_x M[u][x] p[y][x] + 256) >> 9 (4 fraction bits); columns: c[v][u] = (sum_y M[v][y] t[y][u] + 8192)
+ *           >> 14 (3 fraction bits, as libjpeg's coefficients carry), int32, arithmetic shifts.  Quantised:
+ *           sign(c) * ((|c| + 4 q) / (8 q)) - round half away from zero of c / (8 q).
+ * SEGMENTS  the restart interval is the MCUs of one MCU row: every MCU row starts with predictors 0, is padded to a byte with 1-bits
+ *           and followed by RSTm, m = row mod 8, except the last.  One workgroup per (image, MCU row).
+ * CHUNK     '00dc', the file's length (little-endian, 4 bytes), the file, one zero byte when that length is odd.
+ * ARENA     per image: the arena (device pointer, capacity), a cursor (device int64[2]: bytes used, frames written), an index (device
+ *           int64[index_frames][2]: the chunk's offset in the arena and the file's length) and a status word (device int64).  A frame
+ *           that fits is appended at the cursor, which advances; images of one call that share an arena land in the call's order.
+ *           When a frame does not fit (bytes or index entries), nothing of it is written, the cursor stays and the status word
+ *           receives cursor bytes + the chunk's length: the capacity that would have held it.  Nothing else writes the status word.
+ * inerf_jpeg_frame_bound = 8 + header + MCU rows * (blocks per row * 416 + 2) + 2 + 1: a block's worst case is 22 + 63 * 26 bits
+ * = 208 bytes, every one of them FF and stuffed.  A segment's slot in the workspace has that size.
+ * Integer arithmetic only, LDS atomics are ORs, no hand-off between workgroups (the stream orders the three launches): the bytes are
+ * the same on every run.  Nothing is allocated, synchronised or read on the host: capturable into a HIP graph, and every replay
+ * appends a frame.
+ * ------------------------------------------------------------------------------------------- */
+#define INERF_JPEG_MAX_IMAGES 16
+
+typedef struct inerf_jpeg_image {
+    int32_t height;                  /* 1 .. 65535 */
+    int32_t width;                   /* 1 .. 65535 */
+    int32_t channels;                /* 1 (grey) | 3 (RGB in the plane, YCbCr 4:4:4 in the file) */
+    int32_t quality;                 /* 1 .. 100: what `header` was built with */
+    int64_t src_offset;              /* of the plane in src, bytes (a product's `offset`) */
+    const unsigned char* header;     /* device: the bytes of inerf_jpeg_header(height, width, channels, quality) */
+    int32_t header_bytes;            /* their count: 334 | 629 */
+    int32_t reserved;
+    unsigned char* arena;            /* device */
+    int64_t arena_bytes;             /* its capacity, at least header_bytes */
+    int64_t* cursor;                 /* device int64[2], 8-byte aligned: bytes used, frames written */
+    int64_t* index;                  /* device int64[index_frames][2], 8-byte aligned: chunk offset, file length */
+    int64_t index_frames;            /* >= 1 */
+    int64_t* status;                 /* device int64, 8-byte aligned: 0 until a frame did not fit */
+} inerf_jpeg_image;
+
+typedef struct inerf_jpeg_args {
+    const unsigned char* src;        /* the planes, device */
+    int64_t src_bytes;
+    void* workspace;                 /* device, 16-byte aligned, inerf_jpeg_workspace_bytes(args) bytes */
+    int64_t workspace_bytes;
+    int32_t n_images;                /* 0 .. INERF_JPEG_MAX_IMAGES */
+    int32_t reserved;
+    inerf_jpeg_image images[INERF_JPEG_MAX_IMAGES];
+} inerf_jpeg_args;
+
+/* Host only, no HIP call; reads height, width, channels and quality alone: 256 bytes, per segment 16 bytes of bookkeeping and a slot
+ * of blocks per row * 416 + 2 bytes (rounded up to 16).  INERF_E_INVALID: NULL args, n_images outside 0 .. 16, a dimension outside
+ * 1 .. 65535, channels not 1 | 3, a quality outside 1 .. 100. */
+int64_t inerf_jpeg_workspace_bytes(const inerf_jpeg_args* args);
+
+/* Host only: the worst-case chunk length of one frame (see above) - an arena of frames * bound bytes cannot overflow.
+ * INERF_E_INVALID as above. */
+int64_t inerf_jpeg_frame_bound(int32_t height, int32_t width, int32_t channels);
+
+/* Three launches: one workgroup per segment (transform, quantise, code, stuff; 48 KiB of LDS), one workgroup that sums the segment
+ * lengths and reserves the frames' places, one workgroup per segment that copies it to its place.  Checked before any HIP call.
+ * INERF_E_INVALID: what inerf_jpeg_workspace_bytes refuses; src_bytes < 0 or a plane that runs past it; a NULL header, arena, cursor,
+ * index or status; header_bytes that is not the header's length; arena_bytes < header_bytes; index_frames < 1; cursor, index or
+ * status not 8-byte aligned; for n_images > 0 a NULL src or a workspace not 16-byte aligned.  INERF_E_WORKSPACE: a NULL or too small
+ * workspace.  n_images == 0 is a no-op. */
+int inerf_jpeg_encode(const inerf_jpeg_args* args, void* stream);
+
+/* Host only: the quantisation tables of `quality` in natural (row-major) order, as Pillow's Image.quantization reports them.
+ * INERF_E_INVALID: a quality outside 1 .. 100, a NULL pointer. */
+int inerf_jpeg_tables(int32_t quality, unsigned char* luma, unsigned char* chroma);
+
+/* Host only: writes the header (see FILE) to dst and returns its length.  INERF_E_INVALID: a bad shape or quality, a NULL dst, a
+ * capacity below the header's length. */
+int64_t inerf_jpeg_header(int32_t height, int32_t width, int32_t channels, int32_t quality, unsigned char* dst, int64_t capacity);
 
 #ifdef __cplusplus
 }

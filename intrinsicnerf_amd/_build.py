@@ -12,8 +12,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libinerf.so")
 OBJ_DIR = os.path.join(CSRC, "_obj")          # git-ignored and gpurun-ignored: only the linked library travels
-SOURCES = ["pack.cpp", "api.cpp", "mlp.hip", "mlp_f16.hip", "mlp_f16_t128.hip", "mlp_bwd.hip", "mlp_wgrad.hip", "train_api.hip", "ray_ops.hip", "frame_ops.hip", "cluster.hip", "cluster_fit.hip", "refresh.hip", "layered.hip", "losses.hip", "adam.hip", "batch.hip", "grid.hip", "edit.hip", "eval.hip", "mesh.hip", "mcubes.hip", "imq.hip", "frame_vis.hip", "png.hip"]
-HEADERS = [os.path.join(CSRC, "layout.h"), os.path.join(CSRC, "draws.h"), os.path.join(CSRC, "cluster_search.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_f16_dev.h"), os.path.join(CSRC, "mlp_f16_heads.h"), os.path.join(CSRC, "mlp_f16_pp.h"), os.path.join(CSRC, "mlp_f16_probe.h"), os.path.join(CSRC, "mlp_f16_gate.h"), os.path.join(CSRC, "grid.h"), os.path.join(CSRC, "to_u8.h"), os.path.join(CSRC, "sem_label.h"), os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "jet_table.h"), os.path.join(CSRC, "png_huff.h"),
+SOURCES = ["pack.cpp", "api.cpp", "mlp.hip", "mlp_f16.hip", "mlp_f16_t128.hip", "mlp_bwd.hip", "mlp_wgrad.hip", "train_api.hip", "ray_ops.hip", "frame_ops.hip", "cluster.hip", "cluster_fit.hip", "refresh.hip", "layered.hip", "losses.hip", "adam.hip", "batch.hip", "grid.hip", "edit.hip", "eval.hip", "mesh.hip", "mcubes.hip", "imq.hip", "frame_vis.hip", "png.hip", "jpeg.hip"]
+HEADERS = [os.path.join(CSRC, "layout.h"), os.path.join(CSRC, "draws.h"), os.path.join(CSRC, "cluster_search.h"), os.path.join(CSRC, "mlp_common.h"), os.path.join(CSRC, "mlp_f16_dev.h"), os.path.join(CSRC, "mlp_f16_heads.h"), os.path.join(CSRC, "mlp_f16_pp.h"), os.path.join(CSRC, "mlp_f16_probe.h"), os.path.join(CSRC, "mlp_f16_gate.h"), os.path.join(CSRC, "grid.h"), os.path.join(CSRC, "to_u8.h"), os.path.join(CSRC, "sem_label.h"), os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "jet_table.h"), os.path.join(CSRC, "png_huff.h"), os.path.join(CSRC, "jpeg_tables.h"),
            os.path.join(os.path.dirname(PKG_DIR), "include", "inerf.h")]
 # -ffp-contract=off: the reference rounds o + d*z, albedo*shading + residual, near*(1-t) + far*t ... as
 # separate multiplies and adds; fused multiply-adds would move sample positions by an ulp, which the

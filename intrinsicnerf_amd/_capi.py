@@ -10,7 +10,7 @@ import os
 from . import _build
 from ._build import LIB_PATH
 
-ABI_VERSION = 40026         # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
+ABI_VERSION = 40027         # INERF_ABI_VERSION of include/inerf.h these ctypes declarations mirror
 
 OK, E_INVALID, E_UNSUPPORTED, E_WORKSPACE, E_HIP = 0, -1, -2, -3, -4
 VARIANT_OBJECT, VARIANT_SSR = 0, 1
@@ -195,6 +195,24 @@ class PngArgs(C.Structure):
                 ("images", PngImage * PNG_MAX_IMAGES)]
 
 
+class JpegImage(C.Structure):
+    """inerf_jpeg_image: one plane to encode and the stream (header, arena, cursor, index, status) its frame is appended to
+    (include/inerf.h, inerf_jpeg_encode)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("quality", C.c_int32), ("src_offset", C.c_int64),
+                ("header", C.c_void_p), ("header_bytes", C.c_int32), ("reserved", C.c_int32), ("arena", C.c_void_p),
+                ("arena_bytes", C.c_int64), ("cursor", C.c_void_p), ("index", C.c_void_p), ("index_frames", C.c_int64),
+                ("status", C.c_void_p)]
+
+
+JPEG_MAX_IMAGES = 16
+
+
+class JpegArgs(C.Structure):
+    """inerf_jpeg_args: up to 16 planes -> 16 JPEG files in AVI chunks in three launches (include/inerf.h, inerf_jpeg_encode)."""
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("n_images", C.c_int32), ("reserved", C.c_int32), ("images", JpegImage * JPEG_MAX_IMAGES)]
+
+
 DRAW_STREAM_JITTER, DRAW_STREAM_NOISE_COARSE, DRAW_STREAM_U, DRAW_STREAM_NOISE_FINE = 0, 1, 2, 3
 DRAW_PERTURB, DRAW_FINE = 1, 2
 
@@ -317,6 +335,11 @@ SYMBOLS = {
     "inerf_png_workspace_bytes": (_L, [C.POINTER(PngArgs)]),
     "inerf_png_encode": (_I, [C.POINTER(PngArgs), _P]),
     "inerf_png_code_lengths": (_I, [C.POINTER(C.c_uint32), _I, _I, C.POINTER(C.c_ubyte)]),
+    "inerf_jpeg_workspace_bytes": (_L, [C.POINTER(JpegArgs)]),
+    "inerf_jpeg_frame_bound": (_L, [C.c_int32, C.c_int32, C.c_int32]),
+    "inerf_jpeg_encode": (_I, [C.POINTER(JpegArgs), _P]),
+    "inerf_jpeg_tables": (_I, [C.c_int32, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "inerf_jpeg_header": (_L, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_ubyte), _L]),
 }
 
 _lib = None

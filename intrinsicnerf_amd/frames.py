@@ -146,6 +146,183 @@ def encode_png(image, filter=None):
     return out[:int(sizes[0])].cpu().numpy().tobytes()
 
 
+def encode_jpeg(image, quality=90):
+    """The baseline JPEG file (``bytes``) of a device tensor - uint8 [H, W] (grey) or [H, W, 3] (RGB, stored as YCbCr 4:4:4) - encoded
+    on the device (``inerf_jpeg_encode``) into a worst-case arena.  Waits for the file's length, then copies that many bytes."""
+    if not isinstance(image, torch.Tensor):
+        raise TypeError("encode_jpeg takes a device tensor")
+    if not image.is_cuda:
+        raise RuntimeError(f"encode_jpeg: the image lives on {image.device}; JPEG files are encoded only on a HIP device (no CPU / eager "
+                           "fallback exists)")
+    if not (image.dtype == torch.uint8 and (image.dim() == 2 or (image.dim() == 3 and image.shape[2] == 3))):
+        raise ValueError(f"encode_jpeg: dtype {image.dtype}, shape {tuple(image.shape)}")
+    h, w, c = int(image.shape[0]), int(image.shape[1]), 1 if image.dim() == 2 else 3
+    stream = kernels.JpegStream(h, w, c, quality, kernels.jpeg_frame_bound(h, w, c), 1, image.device)
+    kernels.jpeg_encode(image.contiguous().reshape(-1), kernels.jpeg_plan([(h, w, c, quality, 0)]), [stream])
+    state = stream.state.cpu().numpy()          # cursor (2), status, index
+    if state[2] != 0 or state[1] != 1:
+        raise RuntimeError(f"encode_jpeg: the frame was refused (status {int(state[2])}) by an arena of {stream.capacity} bytes")
+    return stream.arena[8:8 + int(state[4])].cpu().numpy().tobytes()
+
+
+def _avi_chunk(tag, data):
+    return tag + struct.pack("<I", len(data)) + data + (b"\0" if len(data) & 1 else b"")
+
+
+def avi_head(entries, movi_bytes, width, height, fps):
+    """``(head, idx1)`` of a Motion-JPEG AVI file whose ``LIST movi`` payload is ``movi_bytes`` long and holds the chunks
+    ``entries`` = [(offset in the payload, JPEG length)]: the file is ``head + payload + idx1``.  ``RIFF 'AVI '``, ``LIST hdrl``
+    with ``avih`` and one ``strl`` (``strh``: vids / MJPG; ``strf``: a BITMAPINFOHEADER with biCompression 'MJPG'), ``LIST movi``,
+    then ``idx1`` with one keyframe entry per frame, offsets counted from the ``movi`` fourcc.  4 GiB or more: ValueError (OpenDML
+    is not written)."""
+    from fractions import Fraction
+    n = len(entries)
+    rate = Fraction(fps).limit_denominator(1000000)
+    if rate <= 0:
+        raise ValueError(f"fps = {fps}")
+    usec = int(round(1e6 / float(fps)))
+    biggest = max([size for _, size in entries], default=0)
+    avih = struct.pack("<14I", usec, int(biggest * float(fps)) & 0xffffffff, 0, 0x10, n, 0, 1, biggest, width, height, 0, 0, 0, 0)
+    strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIiI4H", 0, 0, 0, 0, rate.denominator, rate.numerator, 0, n, biggest, -1, 0, 0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + _avi_chunk(b"strh", strh) + _avi_chunk(b"strf", strf)
+    hdrl = b"LIST" + struct.pack("<I", 4 + 8 + len(avih) + len(strl)) + b"hdrl" + _avi_chunk(b"avih", avih) + strl
+    idx1 = _avi_chunk(b"idx1", b"".join(b"00dc" + struct.pack("<III", 0x10, 4 + offset, size) for offset, size in entries))
+    riff = 4 + len(hdrl) + 12 + movi_bytes + len(idx1)
+    if riff + 8 >= 1 << 32:
+        raise ValueError(f"the AVI file would hold {riff + 8} bytes: 4 GiB or more needs OpenDML, which is not written")
+    head = b"RIFF" + struct.pack("<I", riff) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", 4 + movi_bytes) + b"movi"
+    return head, idx1
+
+
+def avi_bytes(files, width, height, fps=30):
+    """The Motion-JPEG AVI file of a list of JPEG files (``bytes``) - the host side of ``MovieWriter``: each file becomes a '00dc'
+    chunk exactly as the device lays it into the arena."""
+    payload, entries = b"", []
+    for data in files:
+        entries.append((len(payload), len(data)))
+        payload += _avi_chunk(b"00dc", bytes(data))
+    head, idx1 = avi_head(entries, len(payload), width, height, fps)
+    return head + payload + idx1
+
+
+class MovieWriter:
+    """A Motion-JPEG AVI file written from device frames - what ``imageio.mimwrite`` / ``cv2.VideoWriter`` do on the host at the end
+    of the reference's render passes.  Owns the device arena, cursor, index and status word (``kernels.JpegStream``); ``add(plane)``
+    encodes a device uint8 frame ([H, W] or [H, W, 3]) into the arena and waits for nothing; ``close()`` copies the used part of the
+    arena and the index to the host once and writes the file.
+
+    The arena holds ``frames * (header + bytes_per_sample * samples)`` bytes; ``bytes_per_sample=None`` sizes it by
+    ``inerf_jpeg_frame_bound``, so it cannot overflow.  ``frames=None``: 64.  Once ``frames`` frames were added the used part goes to
+    the host (one wait) and the arena is used again, so a longer movie costs one copy per ``frames`` frames.  A frame that did not fit
+    sets the status word: ``close()`` then raises a RuntimeError that names the capacity it needed."""
+
+    def __init__(self, path, shape, channels, fps=30, quality=90, frames=None, bytes_per_sample=1.0, device=None, _tail=0):
+        self.path, self.fps = path, fps
+        self.shape, self.channels, self.quality = (int(shape[0]), int(shape[1])), int(channels), int(quality)
+        if self.channels not in (1, 3):
+            raise ValueError(f"MovieWriter: {channels} channels")
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError(f"MovieWriter on {device}: frames are encoded only on a HIP device (no CPU / eager fallback exists)")
+        self.frames = 64 if frames is None else int(frames)
+        if self.frames < 1:
+            raise ValueError(f"MovieWriter: frames = {frames}")
+        h, w = self.shape
+        self.bound = kernels.jpeg_frame_bound(h, w, self.channels)
+        header = len(kernels.jpeg_header(h, w, self.channels, self.quality))
+        per_frame = self.bound if bytes_per_sample is None else header + int(float(bytes_per_sample) * h * w * self.channels)
+        self.stream = kernels.JpegStream(h, w, self.channels, self.quality, self.frames * per_frame, self.frames, device, tail=_tail)
+        self.plan = kernels.jpeg_plan([(h, w, self.channels, self.quality, 0)])
+        self.workspace = torch.empty(max(self.plan[1], 1), dtype=torch.uint8, device=device)
+        self.count, self.parts, self.entries, self.bytes, self.closed = 0, [], [], 0, False
+
+    def _check(self, plane):
+        want = self.shape + ((3,) if self.channels == 3 else ())
+        if not isinstance(plane, torch.Tensor):
+            raise TypeError("MovieWriter.add takes a device tensor")
+        if not plane.is_cuda:
+            raise RuntimeError(f"MovieWriter.add: the frame lives on {plane.device}; frames are encoded only on a HIP device (no CPU / "
+                               "eager fallback exists)")
+        if plane.dtype != torch.uint8 or tuple(plane.shape) != want:
+            raise ValueError(f"MovieWriter.add: dtype {plane.dtype}, shape {tuple(plane.shape)}; the movie holds uint8 {want}")
+
+    def reserve(self, n=1):
+        """Room for ``n`` more index entries: when the arena's ``frames`` are used up, its used part goes to the host first."""
+        if self.closed:
+            raise RuntimeError("MovieWriter: closed")
+        if n > self.frames:
+            raise ValueError(f"{n} frames in one call; the arena was made for {self.frames}")
+        if self.count + n > self.frames:
+            self._flush()
+        self.count += n
+
+    def add(self, plane):
+        self._check(plane)
+        self.reserve(1)
+        kernels.jpeg_encode(plane.contiguous().reshape(-1), self.plan, [self.stream], workspace=self.workspace)
+
+    def _flush(self):
+        state = self.stream.state.cpu().numpy()
+        used, written, status = int(state[0]), int(state[1]), int(state[2])
+        if status:
+            raise RuntimeError(f"MovieWriter({self.path!r}): a frame did not fit the arena of {self.stream.capacity} bytes ({self.frames} "
+                               f"frames); it needed a capacity of {status} bytes - raise bytes_per_sample, or pass None for the bound")
+        if written != self.count:
+            raise RuntimeError(f"MovieWriter({self.path!r}): {self.count} frames were added, the device wrote {written}")
+        index = state[3:3 + 2 * written].reshape(-1, 2)
+        self.entries += [(self.bytes + int(o), int(n)) for o, n in index]
+        if used:
+            self.parts.append(self.stream.arena[:used].cpu().numpy())
+        self.bytes += used
+        self.stream.state[:2].zero_()
+        self.count = 0
+
+    def close(self):
+        """Writes the file: head, the arena's bytes verbatim as the ``movi`` payload, ``idx1``.  Returns the path."""
+        if self.closed:
+            return self.path
+        self.closed = True
+        self._flush()
+        h, w = self.shape
+        head, idx1 = avi_head(self.entries, self.bytes, w, h, self.fps)
+        with open(self.path, "wb") as f:
+            f.write(head)
+            for part in self.parts:
+                f.write(part.tobytes())
+            f.write(idx1)
+        self.parts = []
+        return self.path
+
+
+def write_movie(path, stack, fps=30, quality=90):
+    """``imageio.mimwrite(path, stack, fps=..., quality=...)`` as a Motion-JPEG AVI file made on the device: ``stack`` is a numpy array
+    or tensor [N, H, W] or [N, H, W, 3], uint8 (a list of equal frames is stacked); batches of up to 16 frames are uploaded and each
+    batch is encoded in one ``inerf_jpeg_encode`` call into one arena.  ``quality``: JPEG quality 1 .. 100.  Returns the path."""
+    if isinstance(stack, (list, tuple)):
+        stack = torch.stack(list(stack)) if all(isinstance(f, torch.Tensor) for f in stack) else np.stack([np.asarray(f) for f in stack])
+    if not isinstance(stack, torch.Tensor):
+        stack = torch.from_numpy(np.ascontiguousarray(stack))
+    if stack.dtype != torch.uint8 or not (stack.dim() == 3 or (stack.dim() == 4 and stack.shape[3] == 3)) or stack.shape[0] < 1:
+        raise ValueError(f"write_movie: dtype {stack.dtype}, shape {tuple(stack.shape)}; expected uint8 [N, H, W] or [N, H, W, 3]")
+    n, h, w = (int(v) for v in stack.shape[:3])
+    c = 1 if stack.dim() == 3 else 3
+    device = stack.device if stack.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    batch = min(n, kernels._capi.JPEG_MAX_IMAGES)
+    writer = MovieWriter(path, (h, w), c, fps=fps, quality=quality, frames=batch, bytes_per_sample=None, device=device)
+    plane = h * w * c
+    plans = {}
+    workspace = None
+    for start in range(0, n, batch):
+        count = min(batch, n - start)
+        src = stack[start:start + count].to(device).contiguous().reshape(-1)
+        if count not in plans:
+            plans[count] = kernels.jpeg_plan([(h, w, c, quality, k * plane) for k in range(count)])
+        writer.reserve(count)
+        workspace = kernels.jpeg_encode(src, plans[count], [writer.stream] * count, workspace=workspace)
+    return writer.close()
+
+
 def to8b(x):
     """(255 * clip(x, 0, 1)).astype(uint8) - run_nerf_helpers.py:13: numpy arrays on the host, device tensors through
     ``inerf_frame_to_u8``."""
@@ -171,13 +348,20 @@ class FrameProducts:
     ``encode=True``: every plane is also encoded to a PNG file on the device (``inerf_png_encode``: three more launches per frame,
     adaptive row filter, one dynamic-Huffman block per 32 KiB segment); the files travel through a second ``FrameStreamer`` in their
     worst-case buffers, with their lengths behind them, and ``files(i)`` hands out ``{name: bytes}``.  ``images(i)`` is unchanged.
+
+    ``movies={product_name: path}`` (with ``fps=`` and ``quality=``): every frame's plane of each named product is also appended to
+    a Motion-JPEG AVI file (``MovieWriter``) - one ``inerf_jpeg_encode`` call per frame for all of them, after the products launch;
+    ``close_movies()`` writes the files (the front-ends' ``render_path`` calls it after the last pose).  A ``u16`` product cannot be
+    a movie.
     """
 
     KINDS = {name: k for k, name in enumerate(kernels._capi.FRAME_KIND_NAMES)}
 
-    def __init__(self, encode=False):
+    def __init__(self, encode=False, movies=None, fps=30, quality=90):
         self.names = None
         self.encode = bool(encode)
+        self.movies, self.fps, self.quality = dict(movies or {}), fps, int(quality)
+        self.writers = []
 
     def begin(self, products, keys, widths, image_shape, device, palette=None):
         """Starts a pass: ``products`` over a pack of ``keys`` / ``widths`` (``pack_maps``) whose rows are the pixels of an
@@ -230,6 +414,27 @@ class FrameProducts:
             self.png_plan = kernels.png_plan(images)
             self.png_workspace = torch.empty(max(self.png_plan[3], 1), dtype=torch.uint8, device=device)
             self.file_streamer, self.files_in_flight, self.host_files = FrameStreamer(device), [], {}
+        if self.movies:
+            self.close_movies()                     # a pass that was begun before: its files are finished first
+            images = []
+            for name in self.movies:
+                if name not in self.names:
+                    raise KeyError(f"movies names the product {name!r}; this pass makes {self.names}")
+                k = self.names.index(name)
+                kind, width = self.kinds[k]
+                if kind == capi.FRAME_U16:
+                    raise ValueError(f"movies names the product {name!r}: a 16-bit plane cannot be a JPEG frame")
+                rgb = kind in (capi.FRAME_PALETTE, capi.FRAME_JET) or width == 3
+                images.append((self.shape[0], self.shape[1], 3 if rgb else 1, self.quality, self.plan[1][k][0]))
+            self.writers = [MovieWriter(path, self.shape, im[2], fps=self.fps, quality=self.quality, device=device)
+                            for path, im in zip(self.movies.values(), images)]
+            self.jpeg_plan = kernels.jpeg_plan(images)
+            self.jpeg_workspace = torch.empty(max(self.jpeg_plan[1], 1), dtype=torch.uint8, device=device)
+
+    def close_movies(self):
+        """Finishes the movie files of the pass (one copy of each arena's used part) and returns their paths."""
+        writers, self.writers = self.writers, []
+        return [w.close() for w in writers]
 
     def add_frame(self, i, pack):
         """Frame ``i``'s pack ([H * W, columns] fp32 on the device) is complete on the current stream: its planes are computed
@@ -258,6 +463,10 @@ class FrameProducts:
             self.files_in_flight.append(int(i))
             if done is not None:
                 self.host_files[self.files_in_flight.pop(0)] = done
+        if self.writers:
+            for w in self.writers:
+                w.reserve(1)
+            kernels.jpeg_encode(out[:self.plan[2]], self.jpeg_plan, [w.stream for w in self.writers], workspace=self.jpeg_workspace)
 
     def files(self, i):
         """``{name: bytes}`` of frame ``i``: each product's complete PNG file (``encode=True``).  Waits for the copies up to frame ``i``

@@ -2217,3 +2217,101 @@ def png_encode(src, plan, out=None, sizes=None, workspace=None):
         rc = _capi.lib().inerf_png_encode(C.byref(a), _stream(src))
     _capi.check(rc, "inerf_png_encode")
     return out, sizes
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Frame movies on the device (csrc/jpeg.hip): up to 16 planes - what ``frame_products`` wrote - become 16 baseline JPEG files, each
+# appended as an AVI chunk to a device-resident stream.  An image is ``(height, width, channels, quality, src_offset)``: channels
+# 1 (grey) | 3 (RGB), quality 1 .. 100
+# ---------------------------------------------------------------------------------------------------------------------
+def jpeg_tables(quality):
+    """Host only (``inerf_jpeg_tables``): ``(luma, chroma)``, uint8 numpy [64] in natural order, of libjpeg's quality rule."""
+    import numpy as np
+    luma, chroma = (C.c_ubyte * 64)(), (C.c_ubyte * 64)()
+    _capi.check(_capi.lib().inerf_jpeg_tables(int(quality), luma, chroma), "inerf_jpeg_tables")
+    return np.frombuffer(bytes(luma), np.uint8), np.frombuffer(bytes(chroma), np.uint8)
+
+
+def jpeg_header(height, width, channels, quality):
+    """Host only (``inerf_jpeg_header``): the bytes in front of every frame's entropy-coded data, SOI to SOS."""
+    buf = (C.c_ubyte * 1024)()
+    n = int(_capi.lib().inerf_jpeg_header(int(height), int(width), int(channels), int(quality), buf, 1024))
+    if n < 0:
+        _capi.check(n, "inerf_jpeg_header")
+    return bytes(buf[:n])
+
+
+def jpeg_frame_bound(height, width, channels):
+    """Host only (``inerf_jpeg_frame_bound``): the worst-case length of one frame's chunk."""
+    n = int(_capi.lib().inerf_jpeg_frame_bound(int(height), int(width), int(channels)))
+    if n < 0:
+        _capi.check(n, "inerf_jpeg_frame_bound")
+    return n
+
+
+class JpegStream:
+    """The device side of one movie: the header every frame starts with, the arena its chunks are appended to, the cursor (bytes
+    used, frames written), the index (chunk offset and file length per frame) and the status word.  ``tail`` bytes behind the
+    arena's capacity and entries behind the index are allocated but never named to the encoder (tests put sentinels there)."""
+
+    def __init__(self, height, width, channels, quality, capacity, frames, device, tail=0):
+        import numpy as np
+        self.shape = (int(height), int(width), int(channels))
+        self.quality, self.capacity, self.frames = int(quality), int(capacity), int(frames)
+        host = jpeg_header(height, width, channels, quality)
+        self.header_bytes = len(host)
+        self.header = torch.from_numpy(np.frombuffer(host, np.uint8).copy()).to(device)
+        self.arena = torch.zeros(self.capacity + int(tail), dtype=torch.uint8, device=device)
+        self.state = torch.zeros(3 + 2 * (self.frames + int(tail)), dtype=torch.int64, device=device)      # cursor, status, index
+        self.cursor, self.status, self.index = self.state[:2], self.state[2:3], self.state[3:].view(-1, 2)
+
+
+def jpeg_plan(images):
+    """Host only (``inerf_jpeg_workspace_bytes``; no device is touched): ``(args, workspace)`` - an inerf_jpeg_args with the images
+    filled in and the workspace's byte count."""
+    images = list(images)
+    if len(images) > _capi.JPEG_MAX_IMAGES:
+        raise ValueError(f"{len(images)} images: one call takes at most {_capi.JPEG_MAX_IMAGES}")
+    a = _capi.JpegArgs()
+    a.n_images = len(images)
+    for k, spec in enumerate(images):
+        im = a.images[k]
+        im.height, im.width, im.channels, im.quality, im.src_offset = (int(v) for v in spec[:5])
+    workspace = int(_capi.lib().inerf_jpeg_workspace_bytes(C.byref(a)))
+    if workspace < 0:
+        _capi.check(workspace, "inerf_jpeg_workspace_bytes")
+    return a, workspace
+
+
+def jpeg_encode(src, plan, streams, workspace=None):
+    """The planes in ``src`` (a contiguous uint8 tensor on the device) as JPEG files appended to ``streams`` (one ``JpegStream`` per
+    image of ``plan``; several images may name one stream and land in order), in the three launches of ``inerf_jpeg_encode``.
+    Nothing waits; the cursors, indices and status words live on the device.  Returns the workspace."""
+    a, need = plan
+    if not (isinstance(src, torch.Tensor) and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()):
+        raise ValueError("src must be a contiguous 1-d uint8 tensor")
+    streams = list(streams)
+    if len(streams) != a.n_images:
+        raise ValueError(f"{len(streams)} streams for {a.n_images} images")
+    named = [("src", src)]
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=src.device)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous uint8 tensor")
+    named.append(("workspace", workspace))
+    for k, s in enumerate(streams):
+        im = a.images[k]
+        if (im.height, im.width, im.channels) != s.shape or im.quality != s.quality:
+            raise ValueError(f"image {k} is {(im.height, im.width, im.channels)} at quality {im.quality}, its stream was made for "
+                             f"{s.shape} at {s.quality}")
+        named += [(f"streams[{k}].arena", s.arena), (f"streams[{k}].state", s.state), (f"streams[{k}].header", s.header)]
+        im.header, im.header_bytes = s.header.data_ptr(), s.header_bytes
+        im.arena, im.arena_bytes = s.arena.data_ptr(), s.capacity
+        im.cursor, im.status, im.index, im.index_frames = s.cursor.data_ptr(), s.status.data_ptr(), s.index.data_ptr(), s.frames
+    device = _eval_devices(named)
+    a.src, a.src_bytes = src.data_ptr(), src.numel()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    with torch.cuda.device(device):
+        rc = _capi.lib().inerf_jpeg_encode(C.byref(a), _stream(src))
+    _capi.check(rc, "inerf_jpeg_encode")
+    return workspace

@@ -71,6 +71,13 @@ files then need no imgviz at run time.
 (``frames.FrameProducts(encode=True)``, csrc/png.hip): ``render_path(savedir=...)`` then writes the bytes it is handed - the same file
 names, the same pixels, other file bytes than the host encoder's.
 
+``--inerf-movies`` (opt-in) binds the name ``imageio`` in the reference's modules that call ``imageio.mimwrite`` (run_nerf.py:822,
+:1051-1052; trainer.py:1088-1093, :1169-1174; the two dataset modules) to a small proxy: ``mimwrite(path, frames, fps=, quality=)``
+writes a Motion-JPEG AVI file on the device (``frames.write_movie``, csrc/jpeg.hip) under the path with its extension replaced by
+``.avi`` and says so once; imageio's ``quality`` 0 .. 10 becomes the JPEG quality ``50 + 5 * quality`` (8 -> 90, 10 -> 100; None -> 75,
+imageio's default 5).  Every other attribute forwards to the real imageio when there is one; on a host without it the proxy also
+stands in for the module, so that the scripts' ``import imageio`` succeeds.
+
 ``prepare(script)`` does everything but run the main block and returns the module (used by the tests).
 """
 import ast
@@ -225,6 +232,71 @@ def rebind_object_level(namespace, with_render_path=False, cluster_fit=False, lo
     return names
 
 
+MOVIE_MODULES = ("run_nerf", "SSR.training.trainer", "SSR.datasets.replica.replica_datasets", "SSR.datasets.scannet.scannet_datasets")
+
+
+def movie_quality(quality):
+    """imageio's ``quality`` (0 .. 10, None: its default 5) as a JPEG quality: 50 + 5 * quality, so 8 -> 90 and 10 -> 100."""
+    q = 5.0 if quality is None else float(quality)
+    if not 0 <= q <= 10:
+        raise ValueError(f"quality = {quality}: imageio takes 0 .. 10")
+    return int(round(50 + 5 * q))
+
+
+class _MovieProxy:
+    """Stands where a reference module holds ``imageio``: ``mimwrite`` / ``mimsave`` write Motion-JPEG AVI files on the device,
+    everything else is the real module's (AttributeError when there is none)."""
+
+    def __init__(self, real):
+        self.__dict__["_real"], self.__dict__["_told"] = real, False
+
+    def mimwrite(self, path, frames_, fps=30, quality=None, **ignored):
+        from . import frames
+        target = os.path.splitext(os.fspath(path))[0] + ".avi"
+        if not self._told:
+            print(f"intrinsicnerf_amd.launch: --inerf-movies writes Motion-JPEG AVI files on the device: {path} becomes {target}",
+                  file=sys.stderr)
+            self.__dict__["_told"] = True
+        return frames.write_movie(target, frames_, fps=fps, quality=movie_quality(quality))
+
+    mimsave = mimwrite
+
+    def __getattr__(self, name):
+        if self._real is None:
+            raise AttributeError(f"imageio is not installed: the --inerf-movies proxy has mimwrite alone, not {name!r}")
+        return getattr(self._real, name)
+
+
+def movie_proxy(real="import"):
+    """The proxy around ``real`` (default: imageio if it can be imported, else nothing)."""
+    if isinstance(real, str):
+        try:
+            real = importlib.import_module("imageio")
+        except ImportError:
+            real = None
+        if isinstance(real, _MovieProxy):
+            return real
+    return _MovieProxy(real)
+
+
+def install_movie_stand_in():
+    """On a host without imageio the proxy is also the module ``imageio``, so that the scripts' imports succeed."""
+    try:
+        importlib.import_module("imageio")
+    except ImportError:
+        sys.modules["imageio"] = movie_proxy(None)
+
+
+def rebind_movies(extra_modules=()):
+    """``imageio`` -> the proxy in every loaded module of MOVIE_MODULES (and ``extra_modules``) that holds it: [module names]."""
+    proxy, bound = movie_proxy(), []
+    for mod in [sys.modules.get(n) for n in MOVIE_MODULES] + list(extra_modules):
+        if mod is not None and hasattr(mod, "imageio") and mod.__name__ not in bound:
+            mod.imageio = proxy
+            bound.append(mod.__name__)
+    return bound
+
+
 EVAL_SYMBOLS = ("calculate_segmentation_metrics", "calculate_depth_metrics")
 EVAL_MODULES = ("SSR.training.trainer", "SSR.training.training_utils")
 
@@ -326,8 +398,10 @@ def _object_eval_notice():
 
 
 def prepare(script, with_render_path=False, cluster_fit=False, losses=False, adam=False, batches=False, draws=False, cluster_refresh=False,
-            evaluate=False, frame_products=False, frame_png=False):
+            evaluate=False, frame_products=False, frame_png=False, movies=False):
     """Load the reference script as a module (without its main block), rebind the render path, return (module, main code)."""
+    if movies:
+        install_movie_stand_in()
     script = os.path.abspath(script)
     kind = _kind(script)
     root = os.path.dirname(script)
@@ -354,6 +428,8 @@ def prepare(script, with_render_path=False, cluster_fit=False, losses=False, ada
         extra = dict(evaluate=True) if evaluate else {}           # (only when given: a stand-in rebind_ssr of the older signature keeps working)
         extra.update(products)
         mod.__dict__["__inerf_bound__"] = rebind_ssr(with_render_path, cluster_fit, losses, adam, batches, draws, cluster_refresh, **extra)
+    if movies:
+        mod.__dict__["__inerf_movies__"] = rebind_movies([mod])
     return mod, main
 
 
@@ -390,6 +466,9 @@ def main(argv=None):
     if frame_png:
         argv.remove("--inerf-frame-png")
         frame_products = True                          # the files are encoded from the products' planes
+    movies = "--inerf-movies" in argv
+    if movies:
+        argv.remove("--inerf-movies")
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
@@ -410,6 +489,8 @@ def main(argv=None):
         extra["frame_products"] = True
     if frame_png:
         extra["frame_png"] = True
+    if movies:
+        extra["movies"] = True
     if extra:
         mod, main_code = prepare(script, with_render_path, cluster_fit, losses, **extra)
     else:

@@ -450,6 +450,8 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     widths = None
 
     def finish(i, frame):
+        if filming and not imaging:
+            products.images(i)          # (handed out once: lets go of the frame's host copy)
         if imaging:         # the five 8-bit images come from the device planes
             planes = products.images(i)
             encoded = products.files(i) if getattr(products, "encode", False) else None      # PNG files made on the device
@@ -481,6 +483,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     # pass for a frame whose pack it could not keep on the device (decided at the first frame, from the pack's real size)
     slim = products is not None and not update_cluster
     imaging = products is not None and savedir is not None            # (without savedir nobody looks at the images)
+    filming = products is not None and bool(getattr(products, "movies", None))      # FrameProducts(movies=...): the planes feed movie files
     evaluating = evaluator is not None and evaluator.begin(render_poses)
     streamer, in_flight = None, []
     for i, c2w in enumerate(render_poses):
@@ -503,7 +506,7 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
         if products is not None and not pack.is_cuda:
             raise RuntimeError(f"render_path(products=...): the rendered maps live on {pack.device}; the frame images are made only on a "
                                "HIP device (no CPU / eager fallback exists)")
-        if imaging:
+        if imaging or filming:
             if i == 0:
                 products.begin([("", "to8b", "rgb_map"), ("a", "to8b", "albedo_map"), ("s", "to8b", "shading_map"),
                                 ("res", "to8b", "residual_map"), ("acc", "thresh", "acc_map", 10.0)],           # run_nerf.py:173
@@ -521,6 +524,8 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     if streamer is not None:
         for frame in streamer.drain():
             finish(in_flight.pop(0), frame)
+    if filming:
+        products.close_movies()
     cluster_manager = None
     if on_device:
         # the sample table was filled frame by frame; the fit reads it where it is, and every kept pack becomes its two 8-bit images

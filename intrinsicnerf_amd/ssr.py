@@ -393,6 +393,8 @@ class SSRRenderMixin:
         if streamer is not None:
             for frame in streamer.drain():
                 finish(in_flight.pop(0), frame)
+        if products is not None and getattr(products, "movies", None):
+            products.close_movies()
         st = lambda name: np.stack(acc[name], 0) if acc[name] else None
         cluster_manager = None
         if on_device:
