@@ -52,8 +52,9 @@ extern "C" {
  * alpha = 1 - exp(-relu(sigma) * dist), so a point with sigma <= 0 has weight +0 and its colours enter every map as 0 * finite.
  * With the flag such a point's raw row is (0, 0, 0, sigma, 0, 0, 0, 0, 0, 0, 0); a point with !(sigma <= 0) - a NaN included - has
  * the row of the ungated call, bit for bit.  Honoured for the object-level network in INERF_PREC_F16X3 without the endpoint
- * feature, and only with a workspace (inerf_encode_mlp_workspace_bytes with the flag: the survivors' records, bounded by
- * INERF_GATE_BYTES, default 2 GiB; inerf_encode_mlp, which has none, returns INERF_E_WORKSPACE); every other configuration runs
+ * feature, and only with a workspace (inerf_encode_mlp_workspace_bytes with the flag: the survivors' records, 1 028 B per point of a
+ * sub-range, bounded by INERF_GATE_BYTES, default 2 GiB - with INERF_FLAG_GATE_PROBE no records: 12 B per point of a sub-range, see
+ * there; inerf_encode_mlp, which has none, returns INERF_E_WORKSPACE); every other configuration runs
  * the ungated kernel.  inerf_render_rays sets it by itself for a pass whose raw tensor the caller does not receive
  * (raw_coarse / raw_fine NULL) and whose noise tensor is NULL (noise is added to sigma before the ReLU); INERF_GATE=0 in the
  * environment turns that off.  The maps are those of the ungated path (a zero-weight term may flip the sign of a zero sum).
@@ -72,6 +73,13 @@ extern "C" {
  * activations are within 1e-3 of the exact ones, so the exact trunk cannot overflow on a point the probe did not flag).  The
  * exact trunk, whose tiles hold candidates of rays from anywhere in a sub-range, raises no flag of its own; the heads do, per point.
  * inerf_render_rays sets it wherever it sets the gate; INERF_PROBE=0 in the environment turns that off.
+ * WORKSPACE.  The candidates take the exact trunk AND the heads in one kernel, so nothing is kept per point but the candidate list
+ * (4 B) and the probe's (s, S) (8 B): inerf_encode_mlp_workspace_bytes, inerf_workspace_bytes and inerf_render_workspace_bytes with this
+ * flag are smaller than with the gate alone by the records and the survivor list (1 028 B per point of a sub-range).  A sub-range holds
+ * INERF_GATE_BYTES / 1 028 points as with the gate alone, or, the variable unset, up to 2^27 points (1.5 GiB).  A candidate with
+ * sigma <= 0 has its heads evaluated and discarded: its row is the gate's, and it raises no flag behind the trunk.
+ * INERF_GATE_FUSED=0 in the environment: the earlier sequence probe -> exact trunk of the list -> heads of the survivors' records, with
+ * the gate's workspace and sub-ranges - the same rows, status words and margin state, bit for bit.
  *
  * THE MARGIN PER NETWORK.  kappa = 2^-6 is one constant for every network.  A caller that keeps a MARGIN STATE next to a packed blob -
  * INERF_GATE_STATE_BYTES of device memory, 8-byte aligned, zeroed when the blob is packed and again whenever it is packed anew - and

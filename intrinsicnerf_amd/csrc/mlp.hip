@@ -416,7 +416,7 @@ static int64_t scratch_bytes(const inerf_net_desc& net, int64_t n_rays, int n_sa
     return gated(net, flags) ? (b + 255) / 256 * 256 : b;
 }
 static int64_t workspace_need(const inerf_net_desc& net, int64_t n_rays, int n_samples, uint32_t flags) {
-    return scratch_bytes(net, n_rays, n_samples, flags) + (gated(net, flags) ? inerf::mlp_gate_plan(n_rays, n_samples).bytes : 0);
+    return scratch_bytes(net, n_rays, n_samples, flags) + (gated(net, flags) ? inerf::mlp_gate_plan(n_rays, n_samples, inerf::mlp_gate_fused(flags)).bytes : 0);
 }
 
 extern "C" int64_t inerf_encode_mlp_workspace_bytes(const inerf_net_desc* net, int64_t n_rays, int n_samples, uint32_t flags) {

@@ -79,11 +79,12 @@ struct MlpParams {
 
 struct GatePlan {
     int64_t rays_per_sub, n_sub;        // sub-ranges of whole rays
-    int64_t idx_off, count_off, bytes;  // workspace: records at 0, point indices, one counter per sub-range
+    int64_t idx_off, count_off, bytes;  // workspace: records at 0, point indices, one counter per sub-range (fused: neither records nor indices)
     int64_t cand_off, cand_count_off;   // ... the probe's candidate list and its counter per sub-range
     int64_t cand_ss_off;                // ... and the candidates' (s, S), 8 B per point of a sub-range (read only with a GateMargin state)
 };
-GatePlan mlp_gate_plan(int64_t n_rays, int n_samples);
+bool mlp_gate_fused(uint32_t flags);                                   // the probe path without records: INERF_FLAG_GATE_PROBE unless INERF_GATE_FUSED=0
+GatePlan mlp_gate_plan(int64_t n_rays, int n_samples, bool fused);     // `fused`: 12 B per point of a sub-range instead of 1 040
 bool mlp_gate_applies(const inerf_net_desc& net, uint32_t flags);      // which launches the flag changes anything for
 int launch_mlp_f16x3_gated(const MlpParams& p, int64_t n_rays, void* gate_ws, bool probe, hipStream_t stream);
 

@@ -102,7 +102,13 @@ int64_t sem_scratch_bytes_t128(int64_t n_points) {
 //   kGridTrunk  (occupancy grid of mesh extraction, both networks: inerf_occupancy_grid) kGateTrunk up to and including sigma on the points of
 //               a lattice: point gp is lattice index ray0 + gp (grid_point(), grid.h; SSR: / xyz_div), and all that leaves is
 //               occ[gp] = 1 - exp(-relu(sigma) grid_dist) and, when asked for, sigma_out[gp] - no raw rows, no records, no atomics.
-enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3, kGridTrunk = 4 };
+//   kGateWhole  (always kListed; the probe path's second launch unless INERF_GATE_FUSED=0) the listed trunk and the gated heads in ONE tile body:
+//               a listed row's h7 goes from the planes straight into the heads - no record, no survivor list.  Position encoding parked in LDS
+//               like the gated trunk's; the direction encoding (and the point's range words) is written once the parked pieces have left the
+//               direction columns, in front of layer 7's GEMM.  Exact sigma goes to the candidate's raw row always, the ten colour channels
+//               only when !(sigma <= 0): every other candidate keeps the probe's zeros, and raises no range flag behind h7 (its heads were not
+//               evaluated at all when they were a launch of their own).  Survivors are counted per workgroup: one atomicAdd at kernel exit.
+enum : int { kWhole = 0, kGateTrunk = 1, kGateHeads = 2, kGateProbe = 3, kGridTrunk = 4, kGateWhole = 5 };
 constexpr int kGateRecordBytes = 2 * kWidth * 2;      // 1 024
 // (the probe's margin, kProbeKappa or a GateMargin state's kappa_in_use: mlp_common.h)
 
@@ -124,7 +130,9 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     static_assert(!kPipe || (!kSsr && !kSave), "the pipelined trunk is the object-level inference form");
     static_assert(kMode == kWhole || kMode == kGridTrunk || (!kSsr && !kSave && !kPipe), "the density gate is the object-level inference form's");
     static_assert(kMode != kGridTrunk || (!kSave && !kPipe), "the occupancy grid is an inference form");
-    static_assert(!kListed || kMode == kGateTrunk, "the candidate list feeds the gated trunk");
+    static_assert(kListed ? kMode == kGateTrunk || kMode == kGateWhole : kMode != kGateWhole, "the candidate list feeds the gated trunk, alone or with the heads behind it");
+    constexpr bool kNoDirAtEncode = kMode == kGateTrunk || kMode == kGateProbe || kMode == kGridTrunk || kMode == kGateWhole;
+    constexpr bool kPointGuard = kMode == kGateHeads || kMode == kGateWhole;      // the heads' range guard is per point (rows from anywhere in the launch)
     constexpr int kParts = 512 / kPtsT;
     // the wide GEMMs' first products take a zero C operand instead of 64 v_mov in front of every GEMM (wide_gemm_h PEEL): +1.3 % same-box,
     // same bits (profiles/r06_peel_ab.txt); the saving form keeps the explicit zeroing like the two-workgroup one
@@ -170,6 +178,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
     // and this wave's count of measured rows, across the tile loop; they leave at kernel exit
     float r_seen = 0.0f;
     int n_seen = 0;
+    int n_kept = 0;                               // listed whole kernel: this wave's survivors, likewise
     const int n_tiles = kMode == kGateHeads || kListed ? (n_rec + kPtsT - 1) / kPtsT : p.n_tiles;
     auto pad_of = [&](int r) { return pad_words(ldst, r); };      // (gated heads: the point's range flags)
     float amax = 0.0f;                            // running maxima of |scaled value| (encoder inputs / layer outputs): the f16 range guard
@@ -185,7 +194,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
         }
         // ---------------- encode -> hi/lo planes (xyz: columns 0..63, dir: columns 256..287) ----------------
-        auto encode = [&](bool with_dir) {
+        auto encode = [&](bool with_dir, bool with_pos = kMode != kGateHeads) {
             int tid_o = tid;
             asm volatile("" : "+v"(tid_o));
             const int pt = tid_o % kPtsT, part = tid_o / kPtsT;
@@ -200,7 +209,8 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             _Float16* row = ldst + pt * kRowD;
             constexpr auto kStore = kMode == kGateProbe ? &hi_store_parked<kPlaneT> : &split_store<kPlaneT>;
             if constexpr (kMode != kGateHeads)        // (the gated heads' rows arrive with h7 in these columns; the grid's point is a lattice point)
-                encode_position<kSsr, kParts, 2, kStore, kPlaneT, kMode == kGridTrunk>(p, r, gp, part, row, amax);
+                if (with_pos) encode_position<kSsr, kParts, 2, kStore, kPlaneT, kMode == kGridTrunk>(p, r, gp, part, row, amax);
+            if constexpr (kMode == kGateWhole) if (!with_pos) amax = 0.0f;      // (the direction's own maximum: the probe's flag speaks for the position)
             if constexpr (kMode != kGateTrunk && kMode != kGateProbe && kMode != kGridTrunk) if (with_dir) {      // (gated trunk: compiled out - the heads kernel encodes its survivors' directions)
                 const int fd = kParts - 1 - part;
                 if (fd < p.l_dir) {
@@ -219,7 +229,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                     for (int c = 3 + 6 * p.l_dir; c < kDirCols; ++c) { row[kColDirD + c] = (_Float16)0.0f; row[kPlaneT + kColDirD + c] = (_Float16)0.0f; }
                 }
             }
-            if constexpr (kMode == kGateHeads) {      // this thread's word of the point's range flags: written by every tile, so never stale
+            if constexpr (kPointGuard) if (with_dir) {      // this thread's word of the point's range flags: written by every tile, so never stale
                 pad_of(pt)[part] = !(amax <= kF16Safe);
                 amax = 0.0f;
             }
@@ -241,7 +251,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
 #ifdef INERF_ABL_NO_ENCODE      // (timing ablation of a development build: the first tile's encoding stays in LDS; results are wrong)
         if (tile == (int)blockIdx.x)
 #endif
-        encode(kMode != kGateTrunk && kMode != kGateProbe && kMode != kGridTrunk);
+        encode(!kNoDirAtEncode);
         __syncthreads();
         // park the encoding for the skip layer (piece q = tid + 512 i of the tile's 2 048 sixteen-byte pieces: plane q / 1024, row (q % 1024) / 8)
         const bool enc_cached = !kSsr && !kSave && kMode == kWhole && p.sem_scratch != nullptr;
@@ -260,7 +270,8 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             }
         }
         // gated trunk: the same pieces parked in LDS (park_encoding, mlp_f16_gate.h)
-        constexpr bool kPark = (kMode == kGateTrunk || kMode == kGridTrunk) && INERF_GATE_TRUNK_PARK;
+        constexpr bool kPark = (kMode == kGateTrunk || kMode == kGridTrunk || kMode == kGateWhole) && INERF_GATE_TRUNK_PARK;
+        static_assert(kMode != kGateWhole || kPark, "the listed whole kernel has no second encoder pass: its direction columns hold the parked pieces");
         if constexpr (kPark) park_encoding<2, 512>(ldst, tid, false);
         auto encode_again = [&]() {         // the encoding back into columns 0..63 (sc0: past the vector L1, whose lines of an earlier tile may be stale)
             if constexpr (kPark) {
@@ -424,10 +435,28 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             }
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[6], 16), xr, 0, 0, lane_t, am1);
             store256(L.trunk[6], true, SAVE_H0 + 6, pf32(L.trunk[7], 16), kWithBits);
+            // listed whole kernel: the direction columns and the pad words are free since the copy-back (two layers' barriers ago) and nothing
+            // reads them before the heads (layer 7's barriers ahead) - the direction encoding and the point's range words, as the gated heads do
+            if constexpr (kMode == kGateWhole) encode(true, false);
             wide_gemm_h<1, 16, 0, kRowD, kPlaneT, true, 4096, 4, 2048, kPeel>(pre1, wb, frag32(L.trunk[7], 16), xr, 0, 0, lane_t, am1);
             if constexpr (kMode == kGateTrunk || kMode == kGridTrunk) store256(L.trunk[7], true, SAVE_H7, pf32(L.trunk[0], 4), kWithBits);
             else                               store256(L.trunk[7], true, SAVE_H7, pf256(L.as1, 16), kWithBits);
         }
+
+        // listed kernels with a GateMargin state: the probe's error on list entry `at` (this lane's row when `valid`), in correctly rounded
+        // operations; a NaN density, an infinite s or S == 0 is not counted and cannot poison the maximum
+        auto measure_margin = [&](bool valid, int at, float sigma) {
+            if (p.gate_state) {                        // (uniform)
+                bool seen = false;
+                if (valid) {
+                    const float2 ss = *reinterpret_cast<const float2*>(p.cand_ss + 2 * (size_t)at);
+                    const float e = __fdiv_rn(fabsf(__fsub_rn(ss.x, sigma)), ss.y);
+                    seen = ss.y > 0.0f && e - e == 0.0f;
+                    if (seen) r_seen = fmaxf(r_seen, e);
+                }
+                n_seen += __popcll(__ballot(seen));
+            }
+        };
 
         // ---------------- density gate: sigma (probe: s and S), the raw rows, the survivors' records or the candidate list ----------------
         if constexpr (kMode == kGateTrunk || kMode == kGateProbe) {
@@ -444,16 +473,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             if constexpr (kListed) {                   // exact sigma into the candidate's raw row, whose other ten channels the probe zeroed
                 my_point[0] = p.cand_idx[valid ? pt16 + lane_t : 0];
                 if (valid) __builtin_nontemporal_store(sigma, p.raw + (size_t)my_point[0] * p.channels + 3);
-                if (p.gate_state) {                    // (uniform) the probe's error on this row, in correctly rounded operations; a NaN density,
-                    bool seen = false;                 // an infinite s or S == 0 is not counted and cannot poison the maximum
-                    if (valid) {
-                        const float2 ss = *reinterpret_cast<const float2*>(p.cand_ss + 2 * (size_t)(pt16 + lane_t));
-                        const float e = __fdiv_rn(fabsf(__fsub_rn(ss.x, sigma)), ss.y);
-                        seen = ss.y > 0.0f && e - e == 0.0f;
-                        if (seen) r_seen = fmaxf(r_seen, e);
-                    }
-                    n_seen += __popcll(__ballot(seen));
-                }
+                measure_margin(valid, pt16 + lane_t, sigma);
             } else {
                 store_sigma_rows(p, pt16, sigma, lane_t);
             }
@@ -502,8 +522,8 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         const bool sem = kSsr && L.sem_rbs > 0;
         // (gated heads: the row's record, whose point is looked up where the row is written)
         const int my_pt = tile * kPtsT + 16 * wave + (lane_t & 15);
-        const bool my_valid = my_pt < (kMode == kGateHeads ? n_rec : p.n_points);
-        float* const out_row = p.raw + (size_t)(my_valid && kMode != kGateHeads ? my_pt : 0) * p.channels;
+        const bool my_valid = my_pt < (kPointGuard ? n_rec : p.n_points);
+        float* const out_row = p.raw + (size_t)(my_valid && !kPointGuard ? my_pt : 0) * p.channels;
         // gated heads, the per-point range guard: every check is of ONE layer (amax2 starts from zero again behind it), and only a wave
         // that saw a value out of range looks up which of its lanes' points it belongs to - from the hi halves themselves, which are
         // what amax2 is the maximum of
@@ -537,9 +557,9 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             if (sem) prefetch_w<1>(pre1, wb, frag128(L.sem1, 16));
             else     prefetch_w<1, 4096>(pre1, wb, frag32(L.feat, 16));
             f16x8 hi[4][2], lo[4][2];
-            if constexpr (kMode == kGateHeads) amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
+            if constexpr (kPointGuard) amax2 = f16x2{(_Float16)0.0f, (_Float16)0.0f};
             to_operands<2, false, 2, !kSave>(am2, inv2, bias2, amax2, hi, lo);
-            if constexpr (kMode == kGateHeads) flag_operands(hi);
+            if constexpr (kPointGuard) flag_operands(hi);
             if constexpr (kSave) {                // the hidden layer as operand fragments, transposed out of the registers (it never touches LDS):
                 int lane_o = lane_t;              // channel group cg of point half ph = the 64-point kernel's wave cg of tile 2 * tile + ph
                 asm volatile("" : "+v"(lane_o));
@@ -582,7 +602,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         {
             WidePreH<1> prev;
             store256(L.feat, false, SAVE_FEAT, [&]() { prefetch_w<1>(prev, wb, frag128(L.views, 18)); }, kNoBits);
-            if constexpr (kMode == kGateHeads) {      // this wave's 32 feature channels of its lanes' four points, complete in the planes behind the barrier
+            if constexpr (kPointGuard) {      // this wave's 32 feature channels of its lanes' four points, complete in the planes behind the barrier
                 if (out_of_range()) {
 #pragma unroll
                     for (int pb = 0; pb < 4; ++pb) {
@@ -606,7 +626,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             else                               prefetch_w<1, 4096>(pre1, wb, frag32(L.trunk[0], 4));
             f16x8 hi[2][2], lo[2][2];
             to_operands<1, false, 2, !kSave>(amv, invv, biasv, amax2, hi, lo);
-            if constexpr (kMode == kGateHeads) flag_operands(hi);
+            if constexpr (kPointGuard) flag_operands(hi);
             if constexpr (kSave) {                // 128 channels: a four-block fragment slot, block cg of point half ph
                 int lane_o = lane_t;
                 asm volatile("" : "+v"(lane_o));
@@ -619,7 +639,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         }
         __syncthreads();                           // feature / dir columns are dead: the exchange area may be written
         bool my_flagged = false;                   // gated heads: the four flag words of this lane's row (their last writer is behind the barrier; the
-        if constexpr (kMode == kGateHeads) {       // next tile's encode writes them again right behind the next one)
+        if constexpr (kPointGuard) {               // next tile's encode writes them again right behind the next one)
             const u32x4 f = *reinterpret_cast<const u32x4*>(pad_of(16 * wave + (lane_t & 15)));
             my_flagged = (f[0] | f[1] | f[2] | f[3]) != 0u;
         }
@@ -673,7 +693,7 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
         }
         // a wave's 16 points x 11 floats are 704 CONTIGUOUS bytes of raw: they leave as 44 sixteen-byte pieces (lanes 0..43, staged in
         // dead columns of the lo plane), every 64-byte sector written once by one instruction
-        const bool whole_rows = kMode != kGateHeads && p.channels == INERF_BASE_CHANNELS && tile * kPtsT + kPtsT <= p.n_points &&
+        const bool whole_rows = !kPointGuard && p.channels == INERF_BASE_CHANNELS && tile * kPtsT + kPtsT <= p.n_points &&
                                 (reinterpret_cast<uintptr_t>(p.raw) & 15) == 0;
         auto stage_row = [&](int r) { return reinterpret_cast<float*>(ldst + kPlaneT + r * kRowD + 128); };      // lo plane, bytes 256..299 of row r
         if (lane_t < 16 && my_valid) {
@@ -704,6 +724,18 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                 __builtin_nontemporal_store(r0, row + 8); __builtin_nontemporal_store(r1, row + 9); __builtin_nontemporal_store(r2, row + 10);
                 if (my_flagged && p.status)
                     atomicOr(p.status + (p.status_rays > 0 ? (p.ray0 + pt / p.n_samples) / p.status_rays : 0), INERF_STATUS_F16_RANGE);
+            } else if constexpr (kMode == kGateWhole) {      // the candidate's exact sigma always; colours and range flag only where the gated heads would have run
+                const int pt = p.cand_idx[my_pt];
+                float* const row = p.raw + (size_t)pt * p.channels;
+                __builtin_nontemporal_store(sig4[0], row + 3);
+                if (!(sig4[0] <= 0.0f)) {
+                    __builtin_nontemporal_store(c0, row + 0); __builtin_nontemporal_store(c1, row + 1); __builtin_nontemporal_store(c2, row + 2);
+                    __builtin_nontemporal_store(a0, row + 4); __builtin_nontemporal_store(a1, row + 5); __builtin_nontemporal_store(a2, row + 6);
+                    __builtin_nontemporal_store(sh, row + 7);
+                    __builtin_nontemporal_store(r0, row + 8); __builtin_nontemporal_store(r1, row + 9); __builtin_nontemporal_store(r2, row + 10);
+                    if (my_flagged && p.status)
+                        atomicOr(p.status + (p.status_rays > 0 ? (p.ray0 + pt / p.n_samples) / p.status_rays : 0), INERF_STATUS_F16_RANGE);
+                }
             } else if (whole_rows) {
                 float* st = stage_row(16 * wave + lane_t);
                 *reinterpret_cast<f32x4*>(st) = f32x4{c0, c1, c2, sig4[0]};
@@ -728,7 +760,12 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
             }
             __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p.raw + (size_t)(tile * kPtsT + 16 * wave) * INERF_BASE_CHANNELS) + lane_t);
         }
-        if constexpr (kMode != kGateHeads) flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
+        if constexpr (kMode == kGateWhole) {       // this wave's survivors, and the probe's error on its sixteen rows
+            const bool valid = lane_t < 16 && my_valid;
+            n_kept += __popcll(__ballot(valid && !(sig4[0] <= 0.0f)));
+            measure_margin(valid, my_pt, sig4[0]);
+        }
+        if constexpr (!kPointGuard) flag_f16_range(p, tile * kPtsT, kPtsT, amax, amax2, lane_t);
         // (the next tile's encode writes bytes 0..127 and 512..575 of the rows, both planes: clear of the exchange area (hi plane, bytes
         // 128..255) and of the staging rows (lo plane, bytes 256..299) this tile's last readers may still be in)
     }
@@ -749,6 +786,17 @@ __device__ __forceinline__ void encode_mlp_t128_tiles(const MlpParams& p) {
                 if (total > 0) atomicAdd(&p.gate_state->observed, total);
             }
         }
+        if constexpr (kMode == kGateWhole) {      // the workgroup's survivors, the same way: one atomicAdd on the sub-range's count
+            __syncthreads();                      // (thread 0 has read the counts above)
+            if (lane == 0) pad_words(ldst, wave)[0] = n_kept;
+            __syncthreads();
+            if (tid == 0) {
+                unsigned int total = 0;
+#pragma unroll
+                for (int g = 0; g < 8; ++g) total += (unsigned int)pad_words(ldst, g)[0];
+                if (total > 0) atomicAdd(p.gate_count, total);
+            }
+        }
     }
     if (kSave && p.act_max) {
         float m = split_upper_bound(amax, amax2) * (1.0f / kActScale);
@@ -766,6 +814,7 @@ __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_f16x3(const MlpParams
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_heads_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateHeads>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_probe_f16(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateProbe>(p); }
 __global__ __launch_bounds__(512, 2) void k_mlp_gate_trunk_listed_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateTrunk, true>(p); }
+__global__ __launch_bounds__(512, 2) void k_mlp_gate_whole_listed_f16x3(const MlpParams p) { encode_mlp_t128_tiles<false, false, false, kGateWhole, true>(p); }
 template <bool kSsr>
 __global__ __launch_bounds__(512, 2) void k_grid_trunk_f16x3(const MlpParams p) { encode_mlp_t128_tiles<kSsr, false, false, kGridTrunk>(p); }
 
@@ -774,33 +823,45 @@ __global__ __launch_bounds__(512, 2) void k_grid_trunk_f16x3(const MlpParams p) 
 namespace inerf {
 
 // ---- the density gate's launcher ----
-// A launch is walked in sub-ranges of whole rays, each as trunk kernel then heads kernel on the same stream (with the probe: probe kernel,
-// listed trunk, heads; the candidate list holds one index per point of a sub-range, so it cannot overflow either).  The record buffer holds one
-// record per POINT of a sub-range - every point surviving is the worst case - so it cannot overflow.  Its size comes from a byte budget:
-// INERF_GATE_BYTES, default 2 GiB = 2 M points = 64 tiles per CU per trunk launch (DESIGN.md 3.1c on the tail that implies).
-static int64_t gate_budget_points() {
+// A launch is walked in sub-ranges of whole rays.  With the probe: probe kernel, then the listed whole kernel, on the same stream - the candidate
+// list holds one index per point of a sub-range, so it cannot overflow, and nothing else is kept per point but the probe's (s, S).
+// The record paths (the gate alone: trunk kernel, heads kernel; INERF_GATE_FUSED=0: probe, listed trunk, heads) hold one 1 KB record per POINT of
+// a sub-range - every point surviving is the worst case - so the record buffer cannot overflow either.  Points per sub-range come from a byte
+// budget of records, INERF_GATE_BYTES / 1 028, on every path (a sub-range is the same whichever path walks it); unset, the record paths take
+// 2 GiB = 2 M points = 64 tiles per CU per trunk launch (DESIGN.md 3.1c on the tail that implies), the fused path kGateFusedPoints.
+constexpr int64_t kGateFusedPoints = (int64_t)1 << 27;      // 12 B per point: at most 1.5 GiB of list and (s, S); a count of points stays an int
+static int64_t gate_budget_points(bool fused) {
     int64_t bytes = (int64_t)2 << 30;
     if (const char* e = getenv("INERF_GATE_BYTES")) {
         const double v = atof(e);
         if (v >= 1.0) bytes = v < 6.0e10 ? (int64_t)v : (int64_t)6.0e10;
+    } else if (fused) {
+        return kGateFusedPoints;
     }
     return bytes / (kGateRecordBytes + 4);
+}
+
+// the probe path without records (the listed whole kernel) unless INERF_GATE_FUSED=0
+bool mlp_gate_fused(uint32_t flags) {
+    const char* const e = getenv("INERF_GATE_FUSED");
+    return (flags & INERF_FLAG_GATE_PROBE) && !(e && e[0] == '0');
 }
 
 bool mlp_gate_applies(const inerf_net_desc& net, uint32_t flags) {
     return net.precision == INERF_PREC_F16X3 && net.variant == INERF_VARIANT_OBJECT && !(flags & INERF_FLAG_ENDPOINT) && !getenv("INERF_F16_KERNEL");
 }
 
-GatePlan mlp_gate_plan(int64_t n_rays, int n_samples) {
+GatePlan mlp_gate_plan(int64_t n_rays, int n_samples, bool fused) {
     GatePlan g{};
     if (n_rays <= 0 || n_samples < 1) return g;
-    const int64_t fit = gate_budget_points() / n_samples;
+    const int64_t fit = gate_budget_points(fused) / n_samples;
     g.rays_per_sub = fit < 1 ? 1 : fit < n_rays ? fit : n_rays;
     g.n_sub = (n_rays + g.rays_per_sub - 1) / g.rays_per_sub;
     const int64_t pts = g.rays_per_sub * n_samples;
     auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    g.idx_off = up(pts * kGateRecordBytes);
-    g.count_off = g.idx_off + up(pts * 4);
+    // (fused: no record region and no survivor list - the counters come first)
+    g.idx_off = fused ? 0 : up(pts * kGateRecordBytes);
+    g.count_off = fused ? 0 : g.idx_off + up(pts * 4);
     // (the probe's candidate list and counters come behind the budgeted part: the sub-ranges are the same with and without the probe)
     g.cand_off = g.count_off + up(g.n_sub * 4);
     g.cand_count_off = g.cand_off + up(pts * 4);
@@ -825,10 +886,12 @@ __global__ void k_gate_margin_begin(GateMargin* st, unsigned long long min_obser
     st->launches += 1u;
 }
 
-// `probe` (INERF_FLAG_GATE_PROBE): probe kernel -> listed trunk -> heads per sub-range instead of trunk -> heads.  With p0.gate_state the probe's
-// margin is that state's (k_gate_margin_begin), the probe lists its candidates' (s, S) and the listed trunk measures them against the exact sigma.
+// `probe` (INERF_FLAG_GATE_PROBE): probe kernel -> listed whole kernel per sub-range (INERF_GATE_FUSED=0: probe kernel -> listed trunk -> heads)
+// instead of trunk -> heads.  With p0.gate_state the probe's margin is that state's (k_gate_margin_begin), the probe lists its candidates' (s, S)
+// and the listed kernel measures them against the exact sigma.
 int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, bool probe, hipStream_t stream) {
-    const GatePlan g = mlp_gate_plan(n_rays, p0.n_samples);
+    const bool fused = mlp_gate_fused(probe ? INERF_FLAG_GATE_PROBE : 0u);
+    const GatePlan g = mlp_gate_plan(n_rays, p0.n_samples, fused);
     char* const ws = static_cast<char*>(gate_ws);
     unsigned int* const counts = reinterpret_cast<unsigned int*>(ws + g.count_off);
     unsigned int* const cand_counts = reinterpret_cast<unsigned int*>(ws + g.cand_count_off);
@@ -839,7 +902,8 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
     if (attr_set.first()) {
         const struct { void (*kernel)(const MlpParams); int lds_bytes; } kernels[] = {
             {k_mlp_gate_trunk_f16x3, kLdsBytesTrunk}, {k_mlp_gate_heads_f16x3, kLdsBytesT}, {k_mlp_gate_probe_f16, kLdsBytesT},
-            {k_mlp_gate_trunk_listed_f16x3, kLdsBytesTrunk}, {k_mlp_gate_probe_wg2_f16, kLdsBytesProbeWg2}};
+            {k_mlp_gate_trunk_listed_f16x3, kLdsBytesTrunk}, {k_mlp_gate_probe_wg2_f16, kLdsBytesProbeWg2},
+            {k_mlp_gate_whole_listed_f16x3, kLdsBytesTrunk}};
         for (const auto& k : kernels) {
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes);
             if (e != hipSuccess) return record(e);
@@ -860,8 +924,8 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
         p.ray0 = (int)r0;
         p.n_points = (int)(nr * p0.n_samples);
         p.n_tiles = (p.n_points + kPtsT - 1) / kPtsT;
-        p.gate_rec = reinterpret_cast<unsigned char*>(ws);
-        p.gate_idx = reinterpret_cast<int*>(ws + g.idx_off);
+        p.gate_rec = fused ? nullptr : reinterpret_cast<unsigned char*>(ws);
+        p.gate_idx = fused ? nullptr : reinterpret_cast<int*>(ws + g.idx_off);
         p.gate_count = counts + s;
         p.cand_idx = reinterpret_cast<int*>(ws + g.cand_off);
         p.cand_count = cand_counts + s;
@@ -876,11 +940,12 @@ int launch_mlp_f16x3_gated(const MlpParams& p0, int64_t n_rays, void* gate_ws, b
             } else {
                 hipLaunchKernelGGL(k_mlp_gate_probe_f16, dim3(grid), dim3(512), kLdsBytesT, stream, p);
             }
-            hipLaunchKernelGGL(k_mlp_gate_trunk_listed_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (persistent: its tile count is on the device)
+            // (persistent: the tile count is on the device)
+            hipLaunchKernelGGL(fused ? k_mlp_gate_whole_listed_f16x3 : k_mlp_gate_trunk_listed_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);
         } else {
             hipLaunchKernelGGL(k_mlp_gate_trunk_f16x3, dim3(grid), dim3(512), kLdsBytesTrunk, stream, p);      // (+ the parked encoding's extension area)
         }
-        hipLaunchKernelGGL(k_mlp_gate_heads_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);      // (persistent: its tile count is on the device)
+        if (!fused) hipLaunchKernelGGL(k_mlp_gate_heads_f16x3, dim3(grid), dim3(512), kLdsBytesT, stream, p);      // (persistent: its tile count is on the device)
     }
     e = hipGetLastError();
     if (e == hipSuccess && getenv("INERF_GATE_LOG")) {      // debug: the survivor share of this launch (synchronises - not for timed runs)

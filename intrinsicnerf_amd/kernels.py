@@ -779,13 +779,19 @@ def coalesced_chunk(n_rays, chunk, n_samples, n_importance, channels, device):
     if device.type == "cuda":
         cap = min(cap, torch.cuda.mem_get_info(device)[0] // 2)
     # the density gate's record buffer (include/inerf.h INERF_FLAG_GATE_COLOUR: at most INERF_GATE_BYTES, default 2 GiB) is a fixed part
-    # of a large launch's workspace, whatever the ray count; a cap below twice that budget is taken as it is (the buffer comes on top)
+    # of a large launch's workspace, whatever the ray count; a cap below twice that budget is taken as it is (the buffer comes on top).
+    # The probe path keeps no records (INERF_FLAG_GATE_PROBE unless INERF_GATE_FUSED=0): its candidate list and (s, S), 12 B per point of
+    # the larger pass, grow with the rays instead
+    gated = os.environ.get("INERF_GATE", "1")[:1] != "0"
+    records = os.environ.get("INERF_PROBE", "1")[:1] == "0" or os.environ.get("INERF_GATE_FUSED", "1")[:1] == "0"
     gate = int(float(os.environ.get("INERF_GATE_BYTES", 2 * 2 ** 30)))
-    if os.environ.get("INERF_GATE", "1")[:1] != "0" and cap >= 2 * gate:
+    if gated and records and cap >= 2 * gate:
         cap -= gate
     s, f = int(n_samples), int(n_samples) + int(n_importance)
     # per ray: z coarse / new / merged, coarse weights, raw of both levels, maps (include/inerf.h: inerf_render_workspace_bytes), + 10 %
     per_ray = int(1.1 * 4 * (s + n_importance + f + s + (s + f) * channels + 2 * (16 + channels)))
+    if gated and not records:
+        per_ray += 12 * f
     rays = min(n_rays, cap // max(per_ray, 1))
     return max(chunk, rays // chunk * chunk if rays < n_rays else -(-n_rays // chunk) * chunk)
 
